@@ -10,10 +10,15 @@ A step = one pass of the hot path over one synthetic UCF-Crime-length video:
 225 clip times x 10 crops = 2250 clip-forwards of (3,16,224,224) fp32 (cfg2), inputs
 resident in HBM before the timed region. N > 1 (cfg4): that ONE video's clip times are split over the ranks
 (`"scaling": "strong"`, `value`), features all-gathered over RCCL and copied to the host (the .npy rows) inside
-the timed region; the weak reading (a whole video per rank) is measured right after it and reported as
-`weak_scaling` in the same line. Prints ONE JSON line on rank 0. At N = 1 the line also carries `train_cfg3`: the anonymizer training
-iteration of BASELINE.json configs[2] (UNet + I3Res50 + CE/triplet, batch 8 x 48 x 112^2), timed per phase after the
-headline measurement (`--no-train` skips it, `--train` runs only it).
+the timed region. Prints ONE JSON line on rank 0.
+
+A plain run sets up, tunes and warms up, times the --steps steps and prints the line (`value`, `ms_per_step`, and the roofline of
+the timed forwards from their HIP events). `--dump-outputs DIR` writes the features of the last timed step to DIR/features.npy.
+`--full` adds everything else the line used to carry, after the headline measurement: the feature rel-L2 against the fp32 CPU oracle
+and the CPU extractor's rate (`--no-cpu-baseline` skips them), the sustained clock under MFMA load, and at N = 1 the f16 activation
+ranges (`--no-act-range`), the anonymised and uint8-frame extractions and `train_cfg3`, the anonymizer training iteration of BASELINE.json
+configs[2] (UNet + I3Res50 + CE/triplet, batch 8 x 48 x 112^2) timed per phase (`--no-train` skips these three, `--train` runs only the
+training iteration); at N > 1 the weak reading (a whole video per rank) as `weak_scaling` (`--no-weak` skips it).
 
 `--dry-run-cpu` rehearses the N > 1 control flow (process group, sharding, barrier, MAX-reduce of the time, rank-0-only JSON) on the
 CPU with the gloo backend and a stub feature extractor: no kernel runs, the numbers mean nothing (tests/test_bench_dry_run.py).
@@ -421,6 +426,27 @@ def _table_hash(table) -> str:
     return hashlib.sha1(repr(sorted((k, sorted(v.items(), key=repr)) for k, v in table.items())).encode()).hexdigest()[:12]
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(path, feats):
+    """`--dump-outputs`: the features of the last timed step as the caller receives them (rank 0's host block, (clip times, crops, F) fp32) -> path/features.npy,
+    so that two builds can be compared output for output on the same synthetic video. Compare them with a tolerance: the tile tuner picks each conv's
+    configuration by its timing in this run, so two runs of one build may settle on different tiles (two runs of the default command: 1.1e-4 relative L2 per row).
+    A block larger than DUMP_LIMIT_BYTES is cut to a fixed, seeded sample of its (clip time x crop) rows, stored as (rows, F) with the row indices beside it in
+    path/feature_rows.npy."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    a = feats.numpy().astype(np.float32, copy=False)
+    if a.nbytes > DUMP_LIMIT_BYTES:
+        rows = a.reshape(-1, a.shape[-1])
+        k = DUMP_LIMIT_BYTES // (rows.shape[1] * 4 + 8)
+        idx = np.sort(np.random.default_rng(0).choice(rows.shape[0], k, replace=False))
+        np.save(os.path.join(path, "feature_rows.npy"), idx.astype(np.float64))
+        a = rows[idx]
+    np.save(os.path.join(path, "features.npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -433,20 +459,25 @@ def main():
     ap.add_argument("--clip-times", type=int, default=225, help="clip times per GPU (7200 frames / 32)")
     ap.add_argument("--crops", type=int, default=10)
     ap.add_argument("--streams", type=int, default=2, help="HIP streams the clip batches alternate over (fills the tail of one forward with the next)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-train", action="store_true", help="skip the cfg3 training-iteration timing appended at N = 1")
+    ap.add_argument("--full", action="store_true", help="after the headline measurement, also the parity and CPU baseline, the clock probe, and the other "
+                                                        "workloads of the line (N = 1: activation ranges, anon_extract, e2e_uint8, train_cfg3; N > 1: weak_scaling)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the features of the last timed step to DIR/features.npy (float32)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the parity check and the CPU extractor's timing")
+    ap.add_argument("--no-train", action="store_true", help="with --full: skip the anonymised, uint8-frame and cfg3 training-iteration timings appended at N = 1")
     ap.add_argument("--train", action="store_true", help="only the cfg3 training-iteration timing (one JSON line)")
     ap.add_argument("--e2e", action="store_true", help="only the uint8-frames -> features measurement (one JSON line)")
     ap.add_argument("--train-hw", type=int, default=112, help="with --train: frame size (112: cfg3; 224: the per-rank batch of cfg5)")
-    ap.add_argument("--no-act-range", action="store_true", help="skip the per-stage max |activation| of one 10-clip forward (f16 head-room: storage saturates at 65504) added to the line at N = 1")
+    ap.add_argument("--no-act-range", action="store_true", help="with --full: skip the per-stage max |activation| of one 10-clip forward (f16 head-room: storage saturates at 65504) added to the line at N = 1")
     ap.add_argument("--dry-run-cpu", action="store_true", help="rehearse the multi-process control flow on CPU/gloo with a stub extractor")
     ap.add_argument("--scaling", default=None, choices=["weak", "strong"],
                     help="strong (default at N > 1; cfg4): ONE video of --clip-times clip times split over the N ranks (BASELINE.json north_star: 'clips of a long video "
-                         "shard across the 8 GPUs'; ragged shards; a rank's shard runs as equal forwards spread over its streams) -- the weak figure is measured right "
-                         "after it and reported as `weak_scaling` in the same line; weak: every rank keeps --clip-times clip times (the video grows with N). "
+                         "shard across the 8 GPUs'; ragged shards; a rank's shard runs as equal forwards spread over its streams) -- with --full the weak figure is measured "
+                         "right after it and reported as `weak_scaling` in the same line; weak: every rank keeps --clip-times clip times (the video grows with N). "
                          "At N = 1 the two are the same workload (reported as \"weak\")")
-    ap.add_argument("--no-weak", action="store_true", help="N > 1, strong: skip the weak-scaling measurement appended to the line")
+    ap.add_argument("--no-weak", action="store_true", help="N > 1, strong, with --full: skip the weak-scaling measurement appended to the line")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # `python bench.py --gpus N` as the driver starts `--gpus 1`: this process has not touched the GPU (importing torch does not) and starts the N ranks as a
@@ -651,10 +682,12 @@ def main():
     tiles_ok, plan, sizes, rank_info = W["tiles_ok"], W["plan"], W["sizes"], W["ranks"]
     total_clips = T_total * args.crops * args.steps
     value = total_clips / dt
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, out)
     # N > 1: the other reading of "clips/s at N GPUs" in the same line -- `value` is cfg4 as BASELINE.json words it (ONE video's clips split over the ranks,
     # total work fixed: "strong"); `weak_scaling` keeps a whole video per rank (per-GPU work fixed), measured right after it with the same barrier / MAX rule
     weak = None
-    if world > 1 and args.scaling == "strong" and not args.no_weak:
+    if args.full and world > 1 and args.scaling == "strong" and not args.no_weak:
         W = None
         W2 = run_workload("weak", args.steps, tune=True)
         weak = {"value": round(W2["T_total"] * args.crops * args.steps / W2["dt"], 2), "unit": "clips/s", "ms_per_step": round(1e3 * W2["dt"] / args.steps, 3),
@@ -720,17 +753,18 @@ def main():
             traffic_all = tj.get("all_traffic_bytes_per_forward")
     # sustained shader clock of THIS box under matrix load (DVFS lowers it below the 2.4 GHz the nominal peak assumes): reported beside the nominal peak, never instead
     clock_mhz = None
-    try:
-        import ctypes as _C
-        from ted_spad_amd import _lib as _L
-        tbuf = torch.zeros(2 * 1024, dtype=torch.int64, device=dev)
-        for _ in range(2):      # ~20 ms each at 1024 workgroups x 4 waves x 4 x 60000 MFMAs; the second one is read
-            _L.check(_L.lib().tedspad_clock_probe(60000, 1024, tbuf.data_ptr(), _C.c_void_p(torch.cuda.current_stream().cuda_stream)), "tedspad_clock_probe")
-        torch.cuda.synchronize()
-        t = tbuf.view(-1, 2).double().cpu()
-        clock_mhz = float((100.0 * t[:, 0] / t[:, 1]).median())
-    except Exception as e:          # a measurement aid only
-        print("clock probe failed: %s" % e, file=sys.stderr)
+    if args.full:
+        try:
+            import ctypes as _C
+            from ted_spad_amd import _lib as _L
+            tbuf = torch.zeros(2 * 1024, dtype=torch.int64, device=dev)
+            for _ in range(2):      # ~20 ms each at 1024 workgroups x 4 waves x 4 x 60000 MFMAs; the second one is read
+                _L.check(_L.lib().tedspad_clock_probe(60000, 1024, tbuf.data_ptr(), _C.c_void_p(torch.cuda.current_stream().cuda_stream)), "tedspad_clock_probe")
+            torch.cuda.synchronize()
+            t = tbuf.view(-1, 2).double().cpu()
+            clock_mhz = float((100.0 * t[:, 0] / t[:, 1]).median())
+        except Exception as e:          # a measurement aid only
+            print("clock probe failed: %s" % e, file=sys.stderr)
     res["roofline"] = {"bound": "mfma", "achieved": round(achieved, 2), "peak": MFMA_PEAK_TFLOPS, "unit": "TFLOP/s",
                        "frac": round(achieved / MFMA_PEAK_TFLOPS, 4), "traffic": traffic,
                        "traffic_all_kernels": traffic_all,      # `traffic` counts the conv kernels of a forward; this one every kernel between its first and last launch (pools, fix-up, average pool)
@@ -741,7 +775,7 @@ def main():
                        "ms_per_forward": round(fwd_ms / n_fwd, 3), "clips_per_forward": max([k for _, k in plan] or [0]), "streams": len(streams)}
 
     # ---- CPU baseline + parity on a bounded sample: the oracle on this box's host cores ------------
-    if not args.no_cpu_baseline:      # the parity check runs at every N (the other ranks wait at the final barrier); the CPU extractor is TIMED at N = 1 only
+    if args.full and not args.no_cpu_baseline:      # the parity check runs at every N (the other ranks wait at the final barrier); the CPU extractor is TIMED at N = 1 only
         from oracle import i3res50_ref, inception_i3d_ref
         ncpu = os.cpu_count() or 1
         cores = min(ncpu, 32)  # measured on the GPU box's host (128 hardware threads): 8/16/32/64/128 threads -> 6.6/9.2/10.2/7.7/4.0 clips/s
@@ -768,7 +802,7 @@ def main():
                                              "%d of the host's %d hardware threads (the fastest thread count measured on this host type)" % (cores, ncpu)}
         res["feature_rel_l2_max"] = float(rel.max())
         res["feature_rel_l2_tol"] = 1e-3
-    if not args.no_act_range and world == 1 and args.arch == "largei3d":
+    if args.full and not args.no_act_range and world == 1 and args.arch == "largei3d":
         taps = {}
         with torch.no_grad():
             ft.i3d._trunk(clips[:10], taps=taps)
@@ -780,7 +814,7 @@ def main():
         sat, bad = ft.i3d.saturation_counts()
         ft.i3d.check_saturation = False
         res["act_saturated"] = {"at_f16_max": sat, "non_finite": bad, "clips": 10}
-    if world == 1 and not args.no_train:
+    if args.full and world == 1 and not args.no_train:
         del clips, W
         torch.cuda.empty_cache()
         res["anon_extract"] = bench_anon_extract(dev)

@@ -30,6 +30,31 @@ def test_single_process_dry_run():
     assert len(lines) == 1 and lines[0]["n_gpus"] == 1 and lines[0]["gather_ok"] and lines[0]["steps"] == 2
 
 
+def test_dump_outputs_writes_the_last_steps_features(tmp_path):
+    """`--dump-outputs DIR`: the (clip times, crops, F) block of the last timed step as DIR/features.npy (float32), equal from run to run; a block over 64 MB
+    is cut to a fixed sample of its rows, whose indices go to DIR/feature_rows.npy."""
+    import numpy as np
+    import torch
+    from ted_spad_amd.synth import synth_clips
+
+    def run(d, clip_times):
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--dry-run-cpu", "--steps", "2", "--warmup", "0", "--clip-times", str(clip_times),
+                            "--crops", "2", "--batch", "4", "--dump-outputs", str(d)], capture_output=True, text=True, timeout=300, cwd=ROOT)
+        assert r.returncode == 0, r.stderr[-2000:]
+        assert len(_json_lines(r.stdout)) == 1
+        return sorted(os.listdir(d)), np.load(d / "features.npy")
+    names, a = run(tmp_path / "a", 5)
+    assert names == ["features.npy"] and a.dtype == np.float32 and a.shape == (5, 2, 2048)
+    want = synth_clips(0, 10, (3, 2, 4, 4)).flatten(1).mean(1, keepdim=True) * torch.linspace(-1.0, 1.0, 2048).view(1, 2048)     # the stub extractor's rows
+    assert np.allclose(a.reshape(10, 2048), want.numpy(), rtol=1e-6, atol=1e-7)
+    assert np.array_equal(run(tmp_path / "b", 5)[1], a)
+    names, s = run(tmp_path / "c", 4500)                          # 9000 rows x 8 KB = 74 MB
+    rows = np.load(tmp_path / "c" / "feature_rows.npy")
+    assert names == ["feature_rows.npy", "features.npy"] and s.dtype == np.float32 and s.shape == (len(rows), 2048) and rows.dtype == np.float64
+    assert s.nbytes + rows.nbytes <= 64 << 20 and len(set(rows.tolist())) == len(rows) and rows.max() < 9000 and (np.diff(rows) > 0).all()
+    assert np.array_equal(run(tmp_path / "d", 4500)[1], s)
+
+
 def test_two_rank_dry_run_prints_one_line_from_rank0():
     env = dict(os.environ, OMP_NUM_THREADS="1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
@@ -59,6 +84,7 @@ def test_two_rank_strong_scaling_dry_run_splits_one_video():
     j = j[0]
     assert j["scaling"] == "strong" and j["n_gpus"] == 2 and j["config"]["clips_per_step"] == 7 * 2
     assert j["gather_ok"] is True and j["tile_table_ok"] is True
+    assert "weak_scaling" not in j                                   # the weak reading is measured with --full only
 
 
 def test_eight_rank_strong_scaling_dry_run_has_the_cfg4_shards():
@@ -84,11 +110,11 @@ def test_eight_rank_strong_scaling_dry_run_has_the_cfg4_shards():
 
 def test_plain_python_launch_with_gpus_2_starts_its_own_ranks():
     """`python bench.py --gpus 2 ...` exactly as `--gpus 1` is started (no torch.distributed.run, WORLD_SIZE unset): the parent starts the two ranks as a child
-    process, relays ONE JSON line and exits 0. N > 1 defaults to strong scaling (cfg4: one video split over the ranks) with the weak figure in the same line."""
+    process, relays ONE JSON line and exits 0. N > 1 defaults to strong scaling (cfg4: one video split over the ranks); with --full the weak figure is in the same line."""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env["OMP_NUM_THREADS"] = "1"
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--dry-run-cpu", "--steps", "2", "--warmup", "1", "--clip-times", "7",
-                        "--crops", "2", "--batch", "4"], capture_output=True, text=True, timeout=600, cwd=ROOT, env=env)
+                        "--crops", "2", "--batch", "4", "--full"], capture_output=True, text=True, timeout=600, cwd=ROOT, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
     j = _json_lines(r.stdout)
     assert len(j) == 1, r.stdout

@@ -169,14 +169,14 @@ def test_unetpp_eval_vs_oracle(unetpp, shape):
         unetpp.eval()
 
 
-def test_anonymized_extraction_with_unetpp(wrapper, unetpp):
+def test_anonymized_extraction_with_unetpp(wrapper, unetpp, tmp_path):
     """The reference's default extraction chain (st_feature_extraction.py:16-37,72-73: fa = unet++ -> Q1 reshape -> ft.i3d.extract_features)
     end to end against the oracles: the 2048-d clip feature within the 1e-3 gate."""
     from oracle import extract_ref, i3res50_ref, unetpp_ref
     from ted_spad_amd import extraction
     vid = [synth_tensor(9, "uppvid%d" % i, (16, 3, 64, 64)) for i in range(3)]
     feats = np.zeros((3, 2048))
-    extraction.extract_features(vid, feats, "/tmp/_upp_feats.npy", unetpp, wrapper, True, False, batch=2)
+    extraction.extract_features(vid, feats, str(tmp_path / "upp_feats.npy"), unetpp, wrapper, True, False, batch=2)
     sd_u = {k: v.cpu() for k, v in unetpp.state_dict().items()}
     sd_i = {k[4:]: v.cpu() for k, v in wrapper.state_dict().items() if k.startswith("i3d.")}
     with torch.no_grad():
@@ -185,7 +185,7 @@ def test_anonymized_extraction_with_unetpp(wrapper, unetpp):
         assert rel_l2(feats[t], ref[t]) < TOL
     # the anonymizer on one clip at a time and the encoder on all three (extraction.feed's fa_batch): the same rows
     feats1 = np.zeros((3, 2048))
-    extraction.extract_features(vid, feats1, "/tmp/_upp_feats1.npy", unetpp, wrapper, True, False, batch=3, fa_batch=1)
+    extraction.extract_features(vid, feats1, str(tmp_path / "upp_feats1.npy"), unetpp, wrapper, True, False, batch=3, fa_batch=1)
     for t in range(3):
         assert rel_l2(feats1[t], ref[t]) < TOL and rel_l2(feats1[t], feats[t]) < TOL
 
