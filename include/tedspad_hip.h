@@ -335,6 +335,17 @@ int32_t tedspad_triplet_fwd_bwd(const float *a, const float *p, const float *n, 
 int32_t tedspad_cross_entropy_fwd_bwd(const float *logits, const int64_t *labels, float *loss, float *row_ws,
                                       float *dlogits, int32_t B, int32_t C, void *stream);
 
+/* Privacy classifier head (privacy_training/train_privacy.py:49-55): nn.Linear(K, N) + nn.BCEWithLogitsLoss() (mean) and their
+ * backward in ONE launch -- replaces head.linear, the loss and the three GEMVs of the fc backward (torch: F.linear,
+ * F.binary_cross_entropy_with_logits, then addmm / mm / sum in autograd). All fp32, deterministic (no float atomics).
+ * f (B, K), W (N, K), bias (N) or NULL, y (B, N) float targets (0/1 or fractional) -> logits (B, N) (NULL: not written),
+ * loss fp32[1] = mean over B*N (unscaled). df (B, K), dW (N, K), db (N): all or none; each = gradient x grad_scale.
+ * W == NULL: logits mode -- f holds the (B, N) logits (K == N, bias / dW / db NULL), df = d(loss)/d(logits) x grad_scale.
+ * B <= 128, N <= 64; with W: K % 4 == 0, f / W / df / dW 16-byte aligned. */
+int32_t tedspad_bce_head_fwd_bwd(const float *f, const float *W, const float *bias, const float *y, float *logits, float *loss,
+                                 float *df, float *dW, float *db, int32_t B, int32_t K, int32_t N, float grad_scale,
+                                 void *stream);
+
 /* ---- training path: train-mode BatchNorm around the conv kernels, backward of the pooling / resize ops ----
  * Reference: autograd of the torch.nn modules of aux_code/models/{large_i3d,unet_parts}.py under
  * fa_model.train() / ft_model.train() (anonymization_training/train_anonymizer.py:73-75,137-139). */

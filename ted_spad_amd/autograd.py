@@ -19,6 +19,7 @@ Modes, as the reference's modules behave under `train()` / `eval()`:
                         eval with an input that requires grad (phase 1): BN folded, gradient w.r.t. the INPUT only
                         (the reference also accumulates never-used weight gradients there)
     fb (ResNet-50+MLP)  train / eval-with-input-gradient likewise
+    fb (ResNet-50+fc)   train: batch-statistics BatchNorm, parameter gradients (privacy_training/train_privacy.py:38-56); eval: unchanged
 """
 from __future__ import annotations
 
@@ -222,6 +223,45 @@ def fb_forward(module, x):
     if module.training:
         return _FBFn.apply(tr, "train", x, *module.parameters())
     return _FBFn.apply(tr, "eval", x)
+
+
+# ---- the privacy classifier: ResNet-50 + fc (build_resnet_predictor) ----------------------------------------------------------
+
+class _PredictorFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, trainer, x, *params):
+        ctx.tape_guard = _Tape(x.device)
+        logits, _, tape = trainer.forward(x)
+        ctx.trainer, ctx.tape = trainer, tape
+        ctx.set_materialize_grads(False)
+        return logits
+
+    @staticmethod
+    def backward(ctx, dlogits):
+        tr = ctx.trainer
+        params = list(tr.m.parameters())
+        if dlogits is None:
+            return (None, None) + (None,) * len(params)
+        ctx.tape_guard.check()
+
+        def run():
+            tr.backward(ctx.tape, _up(dlogits))
+            tr.flush_grads()
+
+        _, grads = _capture_grads(params, run)
+        ctx.tape = None
+        return (None, None) + tuple(_down(grads))
+
+
+def predictor_forward(module, x):
+    """ResNet50 with an fc (load_fb_model(ssl=False)) in train(): train_privacy.py:39,49-55 -- batch-statistics BatchNorm, every parameter
+    gets its gradient through `loss.backward()`."""
+    from .train_nets import PredictorTrainer
+    if x.requires_grad and torch.is_grad_enabled():
+        raise NotImplementedError("ResNet50 predictor: gradient w.r.t. the INPUT images is not built (the reference never needs it: fa is frozen "
+                                  "in train_privacy.py:148-151)")
+    tr = _trainer(module, PredictorTrainer)
+    return _PredictorFn.apply(tr, x, *module.parameters())
 
 
 def freeze_bn(model):

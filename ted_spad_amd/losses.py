@@ -5,6 +5,7 @@ gradients, which `backward` scales by the incoming gradient.
     NTXentLoss(device, batch_size, temperature, use_cosine_similarity)(zis, zjs)   aux_code/nt_xent_original.py:7-70
     TripletMarginLoss(margin=1.0)(anchor, positive, negative)                       train_anonymizer.py:349-350,115
     CrossEntropyLoss()(logits, labels)                                              train_anonymizer.py:347,107
+    BCEWithLogitsLoss()(logits, targets)                                            privacy_training/train_privacy.py:157,52
 
 The reference re-instantiates NTXentLoss (and rebuilds its numpy mask) every iteration
 (train_anonymizer.py:82,155); here the mask is in-kernel.
@@ -14,7 +15,7 @@ import ctypes as C
 import torch
 import torch.nn as nn
 
-from . import _lib
+from . import _lib, head
 from .engine import _stream_ptr, require_cuda
 
 
@@ -109,3 +110,34 @@ class _CEFn(torch.autograd.Function):
 class CrossEntropyLoss(nn.Module):
     def forward(self, logits, labels):
         return _CEFn.apply(logits, labels)
+
+
+class _BCEFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, logits, target):
+        lg = _f32(logits)
+        _, loss, dl, _, _ = head.bce_head(lg.reshape(-1, lg.shape[-1]), target.reshape(-1, lg.shape[-1]))
+        ctx.save_for_backward(dl)
+        ctx.shape = logits.shape
+        return loss[0]
+
+    @staticmethod
+    def backward(ctx, g):
+        (dl,) = ctx.saved_tensors
+        return (dl * g).view(ctx.shape), None
+
+
+class BCEWithLogitsLoss(nn.Module):
+    """nn.BCEWithLogitsLoss() with its defaults (mean reduction, no weight / pos_weight): the value and d(loss)/d(logits) in one launch
+    (the logits mode of tedspad_bce_head_fwd_bwd). Rows of at most 64 logits, at most 128 rows; no gradient w.r.t. the target."""
+
+    def __init__(self, weight=None, size_average=None, reduce=None, reduction="mean", pos_weight=None):
+        super().__init__()
+        if weight is not None or pos_weight is not None or size_average is not None or reduce is not None or reduction != "mean":
+            raise NotImplementedError("BCEWithLogitsLoss: only the default form (mean reduction, no weight / pos_weight) is built; "
+                                      "train_privacy.py:157 uses nothing else")
+
+    def forward(self, logits, target):
+        if logits.shape != target.shape or logits.dim() == 0:
+            raise ValueError("BCEWithLogitsLoss: logits %s and target %s must have the same (non-scalar) shape" % (tuple(logits.shape), tuple(target.shape)))
+        return _BCEFn.apply(logits, target)

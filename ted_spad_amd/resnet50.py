@@ -89,7 +89,8 @@ class ResNet50(nn.Module):
         """(N,3,H,W) fp32 -> (N,2048) fp32: conv1 .. avgpool + flatten (eval-mode BN folded)."""
         if self.training:
             raise NotImplementedError("a bare ResNet50 in train() mode: training goes through the Sequential(ResNet50, MLP) that "
-                                      "load_fb_model(ssl=True) returns (ted_spad_amd/autograd.py) or train_step.AnonymizerTrainStep")
+                                      "load_fb_model(ssl=True) returns (ted_spad_amd/autograd.py) or train_step.AnonymizerTrainStep, "
+                                      "or through forward() of the predictor (num_classes > 0)")
         E.require_cuda(x, "ResNet50")
         if x.dim() != 4 or x.shape[1] != 3 or x.shape[3] % 2:
             raise ValueError("expected (N,3,H,W) with even W, got %s" % (tuple(x.shape),))
@@ -107,6 +108,9 @@ class ResNet50(nn.Module):
         return E.global_avgpool(a)
 
     def forward(self, x):
+        if self.training and isinstance(self.fc, LinearParams):      # the privacy classifier being trained (train_privacy.py:39-56)
+            from . import autograd
+            return autograd.predictor_forward(self, x)
         f = self.features(x)
         if isinstance(self.fc, _Identity):
             return f

@@ -430,6 +430,14 @@ class I3DTrainer:
 # fb: the privacy branch, ResNet-50 + MLP (model_loaders.py:124-153)
 # ------------------------------------------------------------------------------------------------------------------
 
+def _resnet50_trunk(r):
+    """The BottleneckTrunk of a resnet50.ResNet50 (conv1 .. avgpool; torchvision's layout: 7x7/2 stem, 3x3/2 max-pool pad 1)."""
+    dt = r.compute_dtype
+    stem = TE.ConvLayer(r.conv1.weight, None, (1, 2, 2), (0, 3, 3), pair_w=3, dtype=dt)
+    blocks = _bottleneck_blocks([getattr(r, "layer%d" % li) for li in range(1, 5)], dt, temporal=False)
+    return BottleneckTrunk(stem, r.bn1, ((1, 3, 3), (1, 2, 2), (0, 1, 1)), blocks)
+
+
 class FBTrainer:
     """nn.Sequential(ResNet50(fc = Identity), MLP(2048 -> 2048 -> 128, L2-normalised)) with tape:
        mode 'eval'  (phase 1, train_anonymizer.py:75-84: fb frozen, the NT-Xent gradient flows through it into fa)
@@ -437,11 +445,7 @@ class FBTrainer:
 
     def __init__(self, fb_model):
         self.m = fb_model
-        r = fb_model[0]
-        dt = r.compute_dtype
-        stem = TE.ConvLayer(r.conv1.weight, None, (1, 2, 2), (0, 3, 3), pair_w=3, dtype=dt)
-        blocks = _bottleneck_blocks([getattr(r, "layer%d" % li) for li in range(1, 5)], dt, temporal=False)
-        self.trunk = BottleneckTrunk(stem, r.bn1, ((1, 3, 3), (1, 2, 2), (0, 1, 1)), blocks)
+        self.trunk = _resnet50_trunk(fb_model[0])
 
     def conv_layers(self):
         return self.trunk.conv_layers()
@@ -487,6 +491,58 @@ class FBTrainer:
             dx_out = torch.empty(tape["x_shape"], dtype=torch.float32, device=dimg.buf.device)
         TE.act_to_nchw_into(dview, 3, dx_out.unsqueeze(2))
         return dx_out
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# the privacy classifier: ResNet-50 with a multi-label fc (build_resnet_predictor, model_loaders.py:156-165;
+# privacy_training/train_privacy.py:38-56)
+# ------------------------------------------------------------------------------------------------------------------
+
+class PredictorTrainer:
+    """ResNet50(num_classes=N) in train mode with tape: batch-statistics BatchNorm (running statistics moved once per forward), parameter
+    gradients of the trunk and the fc; no gradient w.r.t. the image (the anonymizer in front is frozen, train_privacy.py:148-151)."""
+
+    def __init__(self, resnet50_with_fc):
+        self.m = resnet50_with_fc
+        if not hasattr(resnet50_with_fc.fc, "weight"):
+            raise ValueError("PredictorTrainer needs a ResNet50 with an fc layer (num_classes > 0)")
+        self.trunk = _resnet50_trunk(resnet50_with_fc)
+
+    def conv_layers(self):
+        return self.trunk.conv_layers()
+
+    def flush_grads(self):
+        self.trunk.flush_grads()
+
+    def forward(self, x: torch.Tensor, target: Optional[torch.Tensor] = None, grad_scale: float = 1.0):
+        """x: (B,3,H,W) fp32. Returns (logits (B,N) fp32, loss | None, tape).
+        target (B,N) given: the fc, BCEWithLogitsLoss (mean) and d(loss)/d(f, fc.weight, fc.bias) x grad_scale come from ONE fused launch
+        (head.bce_head) and `backward(tape)` needs no incoming gradient. Without: logits only (the autograd path; the loss is the caller's)."""
+        E.require_cuda(x, "PredictorTrainer")
+        fc = self.m.fc
+        f, tape = self.trunk.forward(E.clip_to_act(x.unsqueeze(2), cpad=4, dtype=self.m.compute_dtype), True)
+        if target is None:
+            return head.linear(f, fc.weight, fc.bias), None, tape
+        logits, loss, tape["df"], tape["dw"], tape["db"] = head.bce_head(f, target, fc.weight, fc.bias, grad_scale=grad_scale)
+        return logits, loss[0], tape
+
+    def grad_buckets(self):
+        """Parameters in the order `backward` finishes them: [fc, layer4, layer3, layer2, layer1, stem]."""
+        return [list(self.m.fc.parameters())] + self.trunk.stage_params()
+
+    def backward(self, tape, dlogits: Optional[torch.Tensor] = None, on_bucket_done=None):
+        """Accumulates every parameter gradient. dlogits (B,N): the gradient w.r.t. the logits of a `forward` without target; None: the
+        fused head's gradients kept in the tape."""
+        fc = self.m.fc
+        if dlogits is not None:
+            df, dw, db = _linear_bwd(tape["f"], fc.weight, dlogits.contiguous().float())
+        else:
+            df, dw, db = tape.pop("df"), tape.pop("dw"), tape.pop("db")
+        _acc_grad(fc.weight, dw)
+        _acc_grad(fc.bias, db)
+        if on_bucket_done is not None:
+            on_bucket_done(0)
+        self.trunk.backward(tape, df, on_stage_done=None if on_bucket_done is None else (lambda k: on_bucket_done(k + 1)))
 
 
 # ------------------------------------------------------------------------------------------------------------------

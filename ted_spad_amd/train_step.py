@@ -108,60 +108,19 @@ class DeviceFlag:
         return "DeviceFlag(%s)" % bool(self)
 
 
-class AnonymizerTrainStep:
-    def __init__(self, fa_model, ft_model, params=DEFAULT_PARAMS, fb_model=None, group=None, loss_scale: float = 256.0):
-        self.fa, self.ft, self.fb, self.params, self.group = fa_model, ft_model, fb_model, params, group
-        self.loss_scale = float(loss_scale)
-        E.apply_env_determinism()
-        self.batch_clips = os.environ.get("TEDSPAD_TRAIN_BATCH_CLIPS", "1") != "0"   # the three clips of an iteration as one ft batch (0: three passes, A/B)
-        self.batch_views = os.environ.get("TEDSPAD_TRAIN_BATCH_VIEWS", "1") != "0"   # the two VISPR views as one fa / fb batch with per-view statistics (0: two passes)
-        self.lazy_losses = os.environ.get("TEDSPAD_TRAIN_LAZY_LOSSES", "0") == "1"
-        self._pin, self._pin_used, self._posted = None, 0, []         # loss read-back (_post / _collect)
-        from .unetpp import UnetPlusPlus
-        self.fa_tr, self.ft_tr = (UNetPPTrainer if isinstance(fa_model, UnetPlusPlus) else UNetTrainer)(fa_model), I3DTrainer(ft_model)
-        self.fb_tr = FBTrainer(fb_model) if fb_model is not None else None
-        self._fa_off_path = self.fa_tr.off_path_params() if hasattr(self.fa_tr, "off_path_params") else []   # unet++: encoder.layer4 (never run)
-        def adam(m, lr):          # torch.optim.Adam as train_anonymizer.py:377-380 builds it; the fused implementation where it exists (same update, one launch per
-            try:                  # parameter group, and it takes the loss scale's non-finite flag on the device: no host sync before the step)
-                return torch.optim.Adam(m.parameters(), lr=lr, fused=True)
-            except (RuntimeError, TypeError, ValueError):
-                return torch.optim.Adam(m.parameters(), lr=lr)
-        self.opt_fa = adam(fa_model, params.learning_rate_fa)
-        self.opt_ft = adam(ft_model, params.learning_rate_ft)
-        self.opt_fb = adam(fb_model, params.learning_rate_fb) if fb_model is not None else None
-        self.ce = CrossEntropyLoss()
-        self.trip = TripletMarginLoss(margin=params.triplet_loss_margin)
-        self.iteration = 0
-        # gradient buckets in the order each backward sequence finishes them (train_nets.*.grad_buckets)
-        self.red_fa = GradBucketReducer(self.fa_tr.grad_buckets(), group, all_params=list(fa_model.parameters()))
-        self.red_ft = GradBucketReducer(self.ft_tr.grad_buckets(), group, all_params=list(ft_model.parameters()))
-        self.red_fb = GradBucketReducer(self.fb_tr.grad_buckets(), group, all_params=list(fb_model.parameters())) if self.fb_tr is not None else None
-        # freeze_bn (train_anonymized_action.py:39-40): gamma / beta of the trunk's BatchNorm3d layers are buffers there -> no gradient
-        self._frozen_bn_params = [p for n_, p in ft_model.named_parameters()
-                                  if n_.startswith("i3d.") and (".bn" in n_ or n_.startswith("i3d.bn") or ".downsample.1." in n_)]
+def fused_adam(m, lr):
+    """torch.optim.Adam as train_anonymizer.py:377-380 builds it; the fused implementation where it exists (same update, one launch per parameter
+    group, and it takes the loss scale's non-finite flag on the device: no host sync before the step)."""
+    try:
+        return torch.optim.Adam(m.parameters(), lr=lr, fused=True)
+    except (RuntimeError, TypeError, ValueError):
+        return torch.optim.Adam(m.parameters(), lr=lr)
 
-    # ---- shared pieces -------------------------------------------------------------------------------------------
-    @staticmethod
-    def _feed(inputs_video):
-        """(B,48,3,H,W) -> the (B*48,3,H,W) pseudo-image batch fa sees (Q2) and the shape to restore."""
-        v = inputs_video.permute(0, 2, 1, 3, 4)                       # :57
-        b, c, t, h, w = v.shape
-        return v.reshape(-1, c, h, w), (b, c, t, h, w)                # :89 (copy: the permuted tensor is not viewable)
 
-    def _views_batchable(self, views) -> bool:
-        """The two VISPR views can run as one batch with per-view BatchNorm statistics: same shape, and every BatchNorm of fa (down to H/16) and fb (down to
-        H/32) sees >= 256 values per channel and view (a conv tile of 256 output rows straddles at most one statistics-group boundary)."""
-        if not self.batch_views or len(views) != 2 or views[0].shape != views[1].shape:
-            return False
-        nb, _, h, w = views[0].shape
-        return nb * (h // 32) * (w // 32) >= 256 and h % 32 == 0 and w % 32 == 0
-
-    def _utility_losses(self, heads, labels):
-        """heads: [(pred, feat)] x3 as leaf tensors -> (loss_ft, loss_ce, loss_trip)."""
-        p = self.params
-        loss_ce = self.ce(heads[0][0], labels)                        # :107
-        loss_trip = self.trip(heads[0][1], heads[1][1], heads[2][1])  # :115
-        return loss_ce + p.temporal_loss_weight * loss_trip, loss_ce, loss_trip
+class StepDriver:
+    """What the step drivers share: the loss read-back (`_post` / `_collect`), the static loss scale (`_scaled` / `_unscale`), the optimizer step
+    with the non-finite skip (`_opt_step`) and the deterministic-mode check. A subclass sets `loss_scale`, `lazy_losses`, `_pin`, `_pin_used`
+    and `_posted` (AnonymizerTrainStep.__init__, privacy.PrivacyTrainStep.__init__)."""
 
     def _post(self, losses: dict):
         """Start reading this step's loss values back NOW: they exist once the forward pass and the loss kernels are queued, long before the backward pass behind
@@ -240,6 +199,57 @@ class AnonymizerTrainStep:
         if E.DETERMINISTIC and E.deterministic_giveups() > 0:
             raise RuntimeError("deterministic mode: %d workgroup(s) gave up their ordered turn in an atomic section during this step; "
                                "its result is not reproducible (call engine.set_deterministic(True) again to re-arm)" % E.deterministic_giveups())
+
+
+class AnonymizerTrainStep(StepDriver):
+    def __init__(self, fa_model, ft_model, params=DEFAULT_PARAMS, fb_model=None, group=None, loss_scale: float = 256.0):
+        self.fa, self.ft, self.fb, self.params, self.group = fa_model, ft_model, fb_model, params, group
+        self.loss_scale = float(loss_scale)
+        E.apply_env_determinism()
+        self.batch_clips = os.environ.get("TEDSPAD_TRAIN_BATCH_CLIPS", "1") != "0"   # the three clips of an iteration as one ft batch (0: three passes, A/B)
+        self.batch_views = os.environ.get("TEDSPAD_TRAIN_BATCH_VIEWS", "1") != "0"   # the two VISPR views as one fa / fb batch with per-view statistics (0: two passes)
+        self.lazy_losses = os.environ.get("TEDSPAD_TRAIN_LAZY_LOSSES", "0") == "1"
+        self._pin, self._pin_used, self._posted = None, 0, []         # loss read-back (_post / _collect)
+        from .unetpp import UnetPlusPlus
+        self.fa_tr, self.ft_tr = (UNetPPTrainer if isinstance(fa_model, UnetPlusPlus) else UNetTrainer)(fa_model), I3DTrainer(ft_model)
+        self.fb_tr = FBTrainer(fb_model) if fb_model is not None else None
+        self._fa_off_path = self.fa_tr.off_path_params() if hasattr(self.fa_tr, "off_path_params") else []   # unet++: encoder.layer4 (never run)
+        self.opt_fa = fused_adam(fa_model, params.learning_rate_fa)
+        self.opt_ft = fused_adam(ft_model, params.learning_rate_ft)
+        self.opt_fb = fused_adam(fb_model, params.learning_rate_fb) if fb_model is not None else None
+        self.ce = CrossEntropyLoss()
+        self.trip = TripletMarginLoss(margin=params.triplet_loss_margin)
+        self.iteration = 0
+        # gradient buckets in the order each backward sequence finishes them (train_nets.*.grad_buckets)
+        self.red_fa = GradBucketReducer(self.fa_tr.grad_buckets(), group, all_params=list(fa_model.parameters()))
+        self.red_ft = GradBucketReducer(self.ft_tr.grad_buckets(), group, all_params=list(ft_model.parameters()))
+        self.red_fb = GradBucketReducer(self.fb_tr.grad_buckets(), group, all_params=list(fb_model.parameters())) if self.fb_tr is not None else None
+        # freeze_bn (train_anonymized_action.py:39-40): gamma / beta of the trunk's BatchNorm3d layers are buffers there -> no gradient
+        self._frozen_bn_params = [p for n_, p in ft_model.named_parameters()
+                                  if n_.startswith("i3d.") and (".bn" in n_ or n_.startswith("i3d.bn") or ".downsample.1." in n_)]
+
+    # ---- shared pieces -------------------------------------------------------------------------------------------
+    @staticmethod
+    def _feed(inputs_video):
+        """(B,48,3,H,W) -> the (B*48,3,H,W) pseudo-image batch fa sees (Q2) and the shape to restore."""
+        v = inputs_video.permute(0, 2, 1, 3, 4)                       # :57
+        b, c, t, h, w = v.shape
+        return v.reshape(-1, c, h, w), (b, c, t, h, w)                # :89 (copy: the permuted tensor is not viewable)
+
+    def _views_batchable(self, views) -> bool:
+        """The two VISPR views can run as one batch with per-view BatchNorm statistics: same shape, and every BatchNorm of fa (down to H/16) and fb (down to
+        H/32) sees >= 256 values per channel and view (a conv tile of 256 output rows straddles at most one statistics-group boundary)."""
+        if not self.batch_views or len(views) != 2 or views[0].shape != views[1].shape:
+            return False
+        nb, _, h, w = views[0].shape
+        return nb * (h // 32) * (w // 32) >= 256 and h % 32 == 0 and w % 32 == 0
+
+    def _utility_losses(self, heads, labels):
+        """heads: [(pred, feat)] x3 as leaf tensors -> (loss_ft, loss_ce, loss_trip)."""
+        p = self.params
+        loss_ce = self.ce(heads[0][0], labels)                        # :107
+        loss_trip = self.trip(heads[0][1], heads[1][1], heads[2][1])  # :115
+        return loss_ce + p.temporal_loss_weight * loss_trip, loss_ce, loss_trip
 
     def _opts(self):
         return [o for o in (self.opt_fa, self.opt_fb, self.opt_ft) if o is not None]
