@@ -549,6 +549,35 @@ int32_t tedspad_segment_pool_mag(const float *feat, int32_t T, int32_t ncrops, i
  * value of the type (f16: what a clamped store writes; bf16: never) into out2[0] and the non-finite ones into out2[1] (both ADDED to). */
 int32_t tedspad_count_saturated(const void *x, int64_t rows, int32_t c, int32_t ldx, int32_t dtype, uint32_t *out2, void *stream);
 
+/* ---- MGFN inference (anomaly_detection_mgfn/models/mgfn.py, utils/utils.py:101-180, model.eval()), all fp32 (csrc/mgfn.hip) ----
+ * Token-major (token, channel) rows over a ragged batch of crop sequences. bounds: int32 (M, 2) = first / one-past-last token of each
+ * token's sequence; seq_off: int32 (nseq + 1) sequence starts. Deterministic, and every result of a sequence depends on that sequence
+ * alone (bit-identical in any batch). */
+/* stats (M, 2) = per-token mean and 1 / (std + eps) (torch_ln == 0: MGFN LayerNorm) or 1 / sqrt(var + eps) (torch_ln != 0: nn.LayerNorm),
+ * biased variance over C channels. C, ldx % 4 == 0. */
+int32_t tedspad_mgfn_ln_stats(const float *x, int32_t ldx, int32_t M, int32_t C, float eps, int32_t torch_ln, float *stats, void *stream);
+/* y[m, n] = sum_{t, c} A[m, t, c] w[n, t * cin + c] + bias[n] (NULL: 0), then exact GELU (gelu != 0), then + res[m, n] (NULL: none).
+ * A[m, t, c] = x[m + t - taps / 2, c], zero outside m's sequence (a Conv1d(k = taps, padding = taps / 2) over time); with stats
+ * (taps == 1 only): (x[m, c] - mean[m]) * rs[m]. f32-input MFMA. N % 64 == 0, cin % 16 == 0, x / w 16-byte aligned, y != x. */
+int32_t tedspad_mgfn_gemm(const float *x, int32_t ldx, const int32_t *bounds, int32_t taps, int32_t cin, const float *stats, const float *w,
+                          const float *bias, int32_t gelu, const float *res, int32_t ldres, float *y, int32_t ldy, int32_t M, int32_t N,
+                          void *stream);
+/* GLANCE attention: qkv rows = q | k | v, each heads x 64 channels (head-blocked, 'b (h d) n'); out[m, h * 64 + d] =
+ * softmax_j((q_m / 8) . k_j) v_j over m's sequence. tmax >= the longest sequence. */
+int32_t tedspad_mgfn_attention(const float *qkv, int32_t ldqkv, const int32_t *seq_off, int32_t nseq, int32_t tmax, int32_t heads, float *out,
+                               int32_t ldo, void *stream);
+/* FOCUS rel_pos: out[m, c] = b[c % heads] + sum_t w[c % heads, t] v[m + t - 2, c] (5 taps, zero outside the sequence; head-interleaved
+ * channels). C, ldv, ldo % 4 == 0, out != v. */
+int32_t tedspad_mgfn_relpos(const float *v, int32_t ldv, const int32_t *bounds, int32_t M, int32_t C, int32_t heads, const float *w,
+                            const float *b, float *out, int32_t ldo, void *stream);
+/* h = nn.LayerNorm(C)(x) (written when h != NULL, (M, C)), logit = h . fc_w + fc_b, score = sigmoid(logit), mag = ||h||_2, each (M). */
+int32_t tedspad_mgfn_head(const float *x, int32_t ldx, int32_t M, int32_t C, const float *ln_w, const float *ln_b, const float *fc_w, float fc_b,
+                          float eps, float *h, float *logit, float *score, float *mag, void *stream);
+/* Crop means: video v owns segments seg_off[v] .. seg_off[v+1] (T_v of them) and tokens ncrops * seg_off[v] + c * T_v + t;
+ * a_out[seg_off[v] + t] = mean_c a[...] (and the same for b when b != NULL). tmax >= max T_v. */
+int32_t tedspad_mgfn_crop_mean(const float *a, float *a_out, const float *b, float *b_out, const int32_t *seg_off, int32_t nvid, int32_t tmax,
+                               int32_t ncrops, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -145,6 +145,34 @@ def synth_state_dict(template: "OrderedDict[str, torch.Tensor]", seed: int = 0,
     return out
 
 
+def synth_mgfn_state_dict(template: "OrderedDict[str, torch.Tensor]", seed: int = 0) -> "OrderedDict[str, torch.Tensor]":
+    """Portable values for an MGFN state_dict (names + shapes from `template`):
+
+    * conv / linear weights (2-D and up): uniform(-a, a), a = sqrt(3 / fan_in);
+    * MGFN LayerNorm `g` and nn.LayerNorm `weight` (1-D): [0.5, 1.5]; biases and LayerNorm `b`: [-0.1, 0.1];
+    * BatchNorm (FOCUS's `norm`) and `num_batches_tracked`: the rules of `synth_state_dict`."""
+    bn_prefixes = {k[: -len("running_mean")] for k in template if k.endswith("running_mean")}
+    bn = synth_state_dict(OrderedDict((k, t) for k, t in template.items() if k[: k.rfind(".") + 1] in bn_prefixes), seed)
+    out = OrderedDict()
+    for k, t in template.items():
+        shape = tuple(t.shape)
+        leaf = k[k.rfind(".") + 1:]
+        if k in bn:
+            out[k] = bn[k]
+            continue
+        if leaf == "weight" and len(shape) >= 2:
+            a = math.sqrt(3.0 / int(np.prod(shape[1:])))
+            v = synth_tensor(seed, k, shape, -a, a)
+        elif leaf == "g" or (leaf == "weight" and len(shape) == 1):
+            v = synth_tensor(seed, k, shape, 0.5, 1.5)
+        elif leaf in ("bias", "b"):
+            v = synth_tensor(seed, k, shape, -0.1, 0.1)
+        else:
+            raise KeyError("synth_mgfn_state_dict: no rule for %s %s" % (k, shape))
+        out[k] = v.to(t.dtype)
+    return out
+
+
 def synth_train_video(seed: int, name: str, shape, device="cpu") -> torch.Tensor:
     """(B,48,3,H,W) training batch in [0,1]: i.i.d. noise frames with a per-sample brightness gain
     (b+1)/B. Pure i.i.d. noise makes the pooled features of all samples nearly identical, and a
