@@ -277,7 +277,11 @@ int32_t tedspad_conv_wgrad(const tedspad_conv_desc *d, const void *x, const void
 /* nn.MaxPool3d / MaxPool3dSamePadding / nn.MaxPool2d: large_i3d.py:138-139, i3d.py:13-45, unet_parts.py:34 */
 int32_t tedspad_maxpool_fwd(const tedspad_pool_desc *d, const void *x, void *y, void *stream);
 /* Same, also recording the window-local index of the FIRST maximum of every output element
- * (uint8, laid out (n,to,ho,wo,c) contiguous) for tedspad_maxpool_bwd. */
+ * (uint8, laid out (n,to,ho,wo,c) contiguous) for tedspad_maxpool_bwd. This is the TRAINING forward: like torch's
+ * max_pool3d it hands non-finite values on -- +-inf is not clamped to the largest finite value, a NaN in a window gives NaN
+ * (index: the last NaN of the window, as torch) -- so that an overflow reaches the loss scale's non-finite check
+ * (tedspad_conv_extras.nosat); tedspad_maxpool_fwd keeps the saturating inference semantics. pad_zero = 1 together with
+ * `idx` is used by no training path and is not covered by the op-level tests. */
 int32_t tedspad_maxpool_fwd_idx(const tedspad_pool_desc *d, const void *x, void *y, uint8_t *idx, void *stream);
 
 /* AdaptiveAvgPool3d(1) / AvgPool3d([2,7,7]) over `spatial` pixels: large_i3d.py:146,262; i3d.py:293,340.
@@ -353,7 +357,7 @@ int32_t tedspad_bce_head_fwd_bwd(const float *f, const float *W, const float *bi
 /* tedspad_bn_finalize + tedspad_scale_shift_act as ONE launch: y = act((z - mean) * gamma * invstd + beta (+ res)) with mean / invstd from the
  * batch sums `stats` ([2][stats_ld]: sum, sum of squares over `count` values per channel); writes mean / invstd (C floats each, kept for the
  * backward pass) and updates running_mean / running_var in place (momentum, unbiased variance; NULL: not tracked). z: (pixels, Cz)
- * with Cz >= C channels per pixel (channels >= C come out as 0); zdtype TEDSPAD_F32, or `dtype` (16-bit conv output, ldz % 8 == 0 -- what
+ * with Cz >= C channels per pixel (channels >= C come out as 0, whatever z and `res` hold there); zdtype TEDSPAD_F32, or `dtype` (16-bit conv output, ldz % 8 == 0 -- what
  * the reference's autocast region holds in front of its BatchNorms, train_anonymizer.py:78,151; the batch sums come from the conv's fp32
  * accumulators either way). nn.BatchNorm{2,3}d in train() mode. */
 int32_t tedspad_bn_train_apply(const void *z, int32_t zdtype, const float *stats, int32_t stats_ld, int64_t count, const float *gamma, const float *beta,

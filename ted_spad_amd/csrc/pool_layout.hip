@@ -44,6 +44,22 @@ template <> __device__ __forceinline__ uint4 max8<BF16>(uint4 a, uint4 b) {
     return pack8<BF16>(fa);
 }
 
+// fp32 -> 16 bits with no clamp and no min / max in the way (either would drop a NaN): the maxima below are input values, so the conversion is exact
+template <typename T>
+__device__ __forceinline__ uint4 pack8_raw(const float (&f)[8]) {
+    uint32_t w[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        uint16_t h[2];
+#pragma unroll
+        for (int j = 0; j < 2; ++j)
+            h[j] = T::kDtype == TEDSPAD_F16 ? __builtin_bit_cast(uint16_t, (_Float16)f[2 * i + j]) : T::from_f32(f[2 * i + j]);
+        w[i] = (uint32_t)h[0] | ((uint32_t)h[1] << 16);
+    }
+    return make_uint4(w[0], w[1], w[2], w[3]);
+}
+
+// The training forward (always called with `idx`; the inference pools are the kernels below and keep their saturating, NaN-dropping packed maxima).
 // max over the window, 8 channels per thread. Padded taps contribute 0 when pad_zero
 // (MaxPool3dSamePadding pads with zeros BEFORE pooling, i3d.py:41-45), else are skipped
 // (nn.MaxPool3d semantics, large_i3d.py:138-139).
@@ -59,8 +75,8 @@ __global__ __launch_bounds__(256) void maxpool_kernel(const PoolKP p) {
         float m[8];
         int am[8];
 #pragma unroll
-        for (int i = 0; i < 8; ++i) { m[i] = -3.0e38f; am[i] = 0; }
-        bool padded = false;
+        for (int i = 0; i < 8; ++i) { m[i] = -__builtin_inff(); am[i] = 0; }
+        bool padded = false, first = true;
         for (int dt = 0; dt < p.kt; ++dt) {
             const int it = to * p.st - p.pt + dt;
             for (int dh = 0; dh < p.kh; ++dh) {
@@ -72,10 +88,13 @@ __global__ __launch_bounds__(256) void maxpool_kernel(const PoolKP p) {
                         float v[8];
                         unpack8<T>(*reinterpret_cast<const uint4 *>(p.x + off), v);
                         const int li = (dt * p.kh + dh) * p.kw + dw;
+                        // torch's max_pool3d rule: the scan starts AT the first tap inside the input; then strict `>`: the first maximum wins; a NaN
+                        // always takes over (the last NaN of the window keeps the index) -- an overflow of the training path stays visible
 #pragma unroll
                         for (int i = 0; i < 8; ++i) {
-                            if (v[i] > m[i]) { m[i] = v[i]; am[i] = li; }   // strict: the first maximum wins (torch semantics)
+                            if (first || v[i] > m[i] || v[i] != v[i]) { m[i] = v[i]; am[i] = li; }
                         }
+                        first = false;
                     } else {
                         padded = true;
                     }
@@ -89,7 +108,7 @@ __global__ __launch_bounds__(256) void maxpool_kernel(const PoolKP p) {
             }
         }
         const size_t opix = (((size_t)n * p.To + to) * p.Ho + ho) * p.Wo + wo;
-        *reinterpret_cast<uint4 *>(p.y + opix * p.ldy + c8 * 8) = pack8<T>(m);
+        *reinterpret_cast<uint4 *>(p.y + opix * p.ldy + c8 * 8) = pack8_raw<T>(m);
         if (p.idx) {
             uint2 pk;
             pk.x = (unsigned)am[0] | ((unsigned)am[1] << 8) | ((unsigned)am[2] << 16) | ((unsigned)am[3] << 24);

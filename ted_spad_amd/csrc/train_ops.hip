@@ -201,6 +201,10 @@ __global__ __launch_bounds__(256) void bn_train_apply_kernel(const void *z, int 
             for (int i = 0; i < 8; ++i) v[i] = v[i] * sc[i] + sf[i];
             if (res) {
                 unpack8<T>(rq[u], r);
+                if (c8s[u] * 8 + 8 > C) {             // the chunk that holds channel C (C < Cz): channels >= C come out as 0 whatever `res` holds there
+#pragma unroll
+                    for (int i = 0; i < 8; ++i) r[i] = c8s[u] * 8 + i < C ? r[i] : 0.f;
+                }
 #pragma unroll
                 for (int i = 0; i < 8; ++i) v[i] += r[i];
             }
@@ -749,6 +753,7 @@ extern "C" int32_t tedspad_bn_bwd_apply(const void *dy, const void *y, const voi
     TS_REQUIRE(dy && z && mean && invstd && gamma && sums && dz && pixels > 0 && C > 0 && C % 8 == 0 && TS_DT(dtype) && (!relu || y || beta) && groups >= 1 && groups < 65536 && TS_ZDT(zdtype, dtype, ldz) && (!dbias || dbias_slots >= 1) && (size_t)C * 16 + 9216 <= 65536,   // [4][C] fp32 terms + the 9 KB reduction image: the default 64 KB dynamic-LDS limit (C <= 3520)
                "tedspad_bn_bwd_apply: bad arguments (relu needs y, or beta to recompute the mask)");
     hipStream_t s = (hipStream_t)stream;
+    // (the grid below decides which `dbias` rows a launch can touch: tests/test_hip_train_kernels.py apply_grid restates grid_for_iters(items, 8) -- change both together)
 #define BWD_APPLY(TT, DD)                                                                                                                            \
     hipLaunchKernelGGL((bn_bwd_apply_kernel<TT, DD>), dim3(grid_for_iters(pixels * (C / 8), 8), groups), dim3(256), (size_t)C * 16, s, (const uint16_t *)dy, (const uint16_t *)y, z, \
                        (int)(zdtype != TEDSPAD_F32), mean, invstd, gamma, beta, sums, sums_ld, 1.f / (float)pixels, (uint16_t *)dz, (uint16_t *)dres, dbias,      \

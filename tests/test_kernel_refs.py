@@ -1,0 +1,152 @@
+"""CPU: the float64 references of tests/kernel_refs.py against float64 torch (autograd) at the shapes the -m gpu op tests use, to 1e-12 relative, and the
+properties of the two value generators those tests rely on (ties in the max-pool windows, exactness of dyadic sums)."""
+import numpy as np
+import pytest
+import torch
+import torch.nn.functional as F
+
+import kernel_refs as R
+from oracle import losses_ref
+from ted_spad_amd.synth import synth_tensor
+
+D = torch.float64
+EPS = 1e-5
+
+
+def close(a, b, rel=1e-12):
+    a, b = torch.as_tensor(a).to(D), torch.as_tensor(b).to(D)
+    assert a.shape == b.shape, (a.shape, b.shape)
+    return float((a - b).abs().max()) <= rel * max(float(b.abs().max()), 1e-300)
+
+
+@pytest.mark.parametrize("C,Cz", R.BN_CHANNELS)
+@pytest.mark.parametrize("pixels", [7, 255, 257, 1000])          # (1 pixel: torch refuses a one-value batch; the formulas are the same)
+def test_bn_refs_vs_torch_autograd(C, Cz, pixels):
+    for relu, with_res, y_mask in ((True, True, True), (True, False, False), (False, False, False)):
+        z, gamma, beta = R.bn_inputs(5, pixels, C, Cz, 1, torch.float32)
+        z = z[0, :, :C].clone().requires_grad_()
+        gamma, beta = gamma.to(D).requires_grad_(), beta.to(D).requires_grad_()
+        res = synth_tensor(5, "res", (pixels, C), -1, 1).to(D).requires_grad_() if with_res else None
+        rm, rv = synth_tensor(5, "rm", (C,), -0.1, 0.1).to(D), synth_tensor(5, "rv", (C,), 0.5, 1.5).to(D)
+        rm_t, rv_t = rm.clone(), rv.clone()
+        u = F.batch_norm(z, rm_t, rv_t, gamma, beta, training=True, momentum=0.1, eps=EPS)
+        y = u + res if with_res else u
+        y = F.relu(y) if relu else y
+        dy = R.dyadic(5, "dy", (pixels, C))
+        y.backward(dy)
+        zd = z.detach()
+        f = R.bn_train_ref(zd, zd.sum(0), (zd * zd).sum(0), pixels, gamma.detach(), beta.detach(), EPS, res.detach() if with_res else None, relu,
+                           momentum=0.1, running_mean=rm, running_var=rv)
+        assert close(f["y"], y.detach()) and close(f["running_mean"], rm_t) and close(f["running_var"], rv_t)
+        assert close(f["mean"], zd.mean(0)) and close(f["invstd"], 1 / torch.sqrt(zd.var(0, unbiased=False) + EPS))
+        assert bool((f["M"] >= f["y"].abs() * (1 - 1e-12)).all())
+        b = R.bn_bwd_ref(dy, f["y"] if y_mask else None, zd, f["mean"], f["invstd"], gamma.detach(), beta.detach(), relu)
+        scale = max(float(z.grad.abs().max()), float(dy.abs().max()))
+        assert float((b["dz"] - z.grad).abs().max()) <= 1e-12 * scale
+        assert close(b["sum_g"], beta.grad) and float((b["sum_gx"] - gamma.grad).abs().max()) <= 1e-12 * float(b["abs_gx"].max())
+        assert close(b["sum_dz"], b["dz"].sum(0)) and bool((b["abs_gx"] >= b["sum_gx"].abs() * (1 - 1e-12)).all())
+        if with_res:
+            assert close(b["dres"], res.grad)
+
+
+def test_bn_mask_recomputed_from_z_equals_mask_from_y():
+    z, gamma, beta = R.bn_inputs(6, 257, 40, 40, 1, torch.float32)
+    f = R.bn_train_ref(z[0], z[0].sum(0), (z[0] ** 2).sum(0), 257, gamma, beta, EPS, None, True)
+    dy = R.dyadic(6, "dy", (257, 40))
+    a = R.bn_bwd_ref(dy, f["y"], z[0], f["mean"], f["invstd"], gamma, beta, True)
+    b = R.bn_bwd_ref(dy, None, z[0], f["mean"], f["invstd"], gamma, beta, True)
+    assert torch.equal(a["g"], b["g"]) and 0.2 < float((a["g"] != 0).double().mean()) < 0.8
+
+
+@pytest.mark.parametrize("case", R.POOL_CASES, ids=[c[0] for c in R.POOL_CASES])
+@pytest.mark.parametrize("c", R.POOL_C)
+def test_maxpool_refs_vs_torch(case, c):
+    _, k, s, p, thw = case
+    x = R.tie_values(7, "px", (2,) + thw + (c,))
+    share = R.maxpool_tie_share(x, k, s, p)
+    assert share >= 0.30, share           # otherwise the GPU test would not be testing ties
+    y, idx = R.maxpool_fwd_ref(x, k, s, p)
+    xt = x.permute(0, 4, 1, 2, 3).contiguous().requires_grad_()
+    yt, it = F.max_pool3d(xt, k, s, p, return_indices=True)
+    assert torch.equal(y, yt.detach().permute(0, 2, 3, 4, 1))
+    assert torch.equal(R.local_to_flat_index(idx, thw, k, s, p), it.permute(0, 2, 3, 4, 1))
+    dy = R.dyadic(7, "pdy", tuple(y.shape))
+    yt.backward(dy.permute(0, 4, 1, 2, 3))
+    add = R.dyadic(7, "padd", tuple(x.shape))
+    assert torch.equal(R.maxpool_bwd_ref(x, idx, dy, k, s, p), xt.grad.permute(0, 2, 3, 4, 1))
+    assert torch.equal(R.maxpool_bwd_ref(x, idx, dy, k, s, p, add=add, relu_mask=True), (xt.grad.permute(0, 2, 3, 4, 1) + add) * (x > 0))
+
+
+def test_maxpool_ref_nonfinite_follows_torch():
+    k, s, p, thw = (1, 3, 3), (1, 2, 2), (0, 1, 1), (1, 6, 6)
+    x = R.tie_values(8, "nf", (1,) + thw + (8,))
+    x[0, 0, 0, 0, :] = float("inf")
+    x[0, 0, 2, 3, 0], x[0, 0, 3, 3, 0] = float("nan"), float("nan")        # two NaNs in one window: the last one keeps the index
+    x[0, 0, 5, 5, :] = float("-inf")
+    y, idx = R.maxpool_fwd_ref(x, k, s, p)
+    yt, it = F.max_pool3d(x.permute(0, 4, 1, 2, 3).contiguous(), k, s, p, return_indices=True)
+    yt = yt.permute(0, 2, 3, 4, 1)
+    assert torch.equal(torch.isnan(y), torch.isnan(yt)) and torch.equal(torch.nan_to_num(y, 7.0), torch.nan_to_num(yt, 7.0))
+    assert torch.equal(R.local_to_flat_index(idx, thw, k, s, p), it.permute(0, 2, 3, 4, 1))
+    assert bool(torch.isinf(y[0, 0, 0, 0]).all()) and int(torch.isnan(y).sum()) >= 2
+
+
+def test_generators():
+    t = R.tie_values(1, "t", (4096,))
+    assert set(t.tolist()) == {0.0, 0.5, 1.0} and 0.45 < float((t == 0).double().mean()) < 0.55
+    for dt in (torch.float16, torch.bfloat16):
+        assert torch.equal(t.to(dt).to(D), t)
+    d = R.dyadic(1, "d", (2000, 8))
+    assert float(d.min()) == -2.0 and float(d.max()) == 2.0 and torch.equal(d * 16, (d * 16).round())
+    assert torch.equal(d.float().sum(0).double(), d.sum(0))               # exact in fp32, in any order
+    for dt in (torch.float16, torch.bfloat16):
+        assert torch.equal(d.to(dt).to(D), d)
+
+
+@pytest.mark.parametrize("h,w,ho,wo", R.BILINEAR_CASES)
+def test_resize_refs(h, w, ho, wo):
+    x = synth_tensor(9, "bx", (2, h, w, 8), -1, 1).to(D)
+    up, taps = R.bilinear2x_ref(x, ho, wo)
+    pt, pl = R.bilinear_pad(h, w, ho, wo)
+    inner = torch.zeros(ho, wo, dtype=torch.bool)
+    inner[pt:pt + 2 * h, pl:pl + 2 * w] = True
+    assert float(up[:, ~inner].abs().max() if (~inner).any() else 0.0) == 0.0
+    assert bool((taps + 1e-15 >= up.abs()).all())                         # a convex combination of the four taps
+    g = R.dyadic(9, "bg", (2, ho, wo, 8))
+    dx = R.bilinear2x_bwd_ref(g, h, w)
+    assert close((dx * x).sum(), (up * g).sum())                   # the adjoint of a linear map
+    n2 = R.nearest2x_ref(x)
+    assert torch.equal(n2[:, 1::2, 0::2], x) and torch.equal(n2[:, 0::2, 1::2], x)
+    assert close((R.nearest2x_bwd_ref(g[:, :2 * h, :2 * w]) * x).sum(), (n2 * g[:, :2 * h, :2 * w]).sum())
+
+
+@pytest.mark.parametrize("B", [1, 2, 3, 24])
+def test_bn1d_and_normalize_refs(B):
+    C = 255
+    x, g, b = synth_tensor(3, "x", (B, C), -2, 2), synth_tensor(3, "g", (C,), 0.5, 1.5), synth_tensor(3, "b", (C,), -0.5, 0.5)
+    dy = synth_tensor(3, "dy", (B, C), -1, 1)
+    f = R.bn1d_train_ref(x, g, b, EPS, True, dy)
+    xd = x.to(D)
+    xh = (xd - f["mean"]) * f["invstd"]
+    assert close(f["y"], (xh * g + b).clamp_min(0))
+    gm = dy.to(D) * (f["y"] > 0)
+    assert close(f["dbeta"], gm.sum(0)) and float((f["dgamma"] - (gm * xh).sum(0)).abs().max()) < 1e-12 * float((gm * xh).abs().sum(0).max() + 1)
+    want = g.to(D) * f["invstd"] * (gm - gm.mean(0) - xh * (gm * xh).mean(0))
+    assert float((f["dx"] - want).abs().max()) < 1e-12 * float(want.abs().max() + gm.abs().max() * float((g.to(D) * f["invstd"]).max()))
+    y, dx = R.l2_normalize_ref(x, 1e-12, dy)
+    nr = xd.norm(dim=1, keepdim=True)
+    assert close(y, xd / nr) and close(dx, (dy.to(D) - y * (y * dy.to(D)).sum(1, keepdim=True)) / nr)
+    z = torch.zeros(2, 5)
+    z[1] = 1e-14 / 5 ** 0.5
+    y, dx = R.l2_normalize_ref(z, 1e-12, torch.ones(2, 5))
+    assert close(y, z.to(D) / 1e-12) and close(dx, torch.ones(2, 5, dtype=D) / 1e-12)      # below eps: y = x / eps, dx = dy / eps
+
+
+def test_loss_refs_vs_numpy_restatements():
+    lg, lab = synth_tensor(2, "lg", (5, 65), -3, 3), torch.tensor([0, 64, 3, 3, 17])
+    assert abs(float(R.cross_entropy_ref(lg, lab)[0]) - losses_ref.cross_entropy_np(lg.numpy(), lab.numpy())) < 1e-12
+    a, p, n = (synth_tensor(2, s, (6, 65), -1, 1) for s in "apn")
+    assert abs(float(R.triplet_ref(a, p, n)[0]) - losses_ref.triplet_np(a.numpy(), p.numpy(), n.numpy())) < 1e-12
+    zi, zj = synth_tensor(2, "zi", (12, 64), -1, 1) * 0.3, synth_tensor(2, "zj", (12, 64), -1, 1) * 0.3
+    for cos in (False, True):
+        assert abs(float(R.ntxent_ref(zi, zj, 0.1, cos)[0]) - losses_ref.nt_xent_np(zi.numpy(), zj.numpy(), 0.1, use_cosine=cos)) < 1e-12 * max(1.0, abs(float(R.ntxent_ref(zi, zj, 0.1, cos)[0])))
