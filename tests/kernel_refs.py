@@ -1,5 +1,5 @@
 """float64 references of the memory-bound training kernels (csrc/train_ops.hip, the idx / backward half of csrc/pool_layout.hip, csrc/head.hip, csrc/loss.hip)
-and the two value generators their tests use. A plain helper module: tests/test_kernel_refs.py checks every reference here against float64 torch (autograd) on
+and the two value generators their tests use; at the end, the exact-arithmetic conv references and case tables of tests/test_hip_conv_exact.py. A plain helper module: tests/test_kernel_refs.py checks every reference here against float64 torch (autograd) on
 the CPU, the -m gpu op tests (test_hip_train_kernels.py, test_hip_head_ops.py, test_hip_losses.py) compare the kernels with them.
 
 Activations are channels-last: (pixels, C) for the BatchNorm kernels, (n, t, h, w, c) for the pools, (n, h, w, c) for the resizes. Everything returned is a
@@ -304,3 +304,216 @@ def bn_inputs(seed, pixels, C, Cz, groups, dt):
     gamma = torch.where(synth_tensor(seed, "bngs", (C,)) < 0.25, -gamma, gamma)       # some negative scales
     beta = synth_tensor(seed, "bnb", (C,), -0.5, 0.5)
     return z, gamma, beta
+
+
+# ---- exact-arithmetic conv references (tests/test_hip_conv_exact.py) ------------------------------------------------------------------------------------
+# Small-integer operands make every product and every partial sum of the conv kernels an integer below 2^24: exact in fp32 whatever the order of the float
+# atomics, the K order of a tile, the pixel splits or the MFMA shape. The kernels must then equal these float64 references BIT FOR BIT (rounded once where
+# the output is 16-bit). Tensors are (n, c, t, h, w) float64; weights (co, ci, kt, kh, kw); pads are (t, h, w) FRONT / BACK zero padding.
+def small_ints(seed, name, shape, lo=-2, hi=2, density=0.5):
+    """Integers in [lo, hi], a share 1 - density of them forced to 0: exact in f16 and bf16."""
+    u = synth_tensor(seed, name, shape).to(D)
+    keep = synth_tensor(seed, name + "/keep", shape).to(D) < density
+    return (torch.floor(u * (hi - lo + 1)).clamp_(0, hi - lo) + lo) * keep
+
+
+def _pad5(x, pf, pb):
+    return F.pad(x, [pf[2], pb[2], pf[1], pb[1], pf[0], pb[0]])
+
+
+def _chan(v):
+    return torch.as_tensor(v).to(D).view(1, -1, 1, 1, 1)
+
+
+def _epilogue(v, residual, mask, relu):
+    if residual is not None:
+        v = v + residual.to(D)
+    if relu:
+        v = v.clamp_min(0.0)
+    if mask is not None:
+        v = torch.where(mask.to(D) > 0, v, torch.zeros_like(v))
+    return v
+
+
+def conv_fwd_ref64(x, w, stride, pf, pb, scale=None, shift=None, residual=None, mask=None, relu=False):
+    """(y, z): z = scale[co] * conv3d(x, w) + shift[co] (what `stats` and a plain `y32` see), y = mask > 0 ? act(z + residual) : 0."""
+    z = F.conv3d(_pad5(x.to(D), pf, pb), w.to(D), stride=tuple(stride))
+    if scale is not None:
+        z = z * _chan(scale)
+    if shift is not None:
+        z = z + _chan(shift)
+    return _epilogue(z, residual, mask, relu), z
+
+
+def conv_dgrad_ref64(dy, w, x_shape, stride, pf, pb, scale=None, residual=None, mask=None, relu=False):
+    """d(x) of y = conv3d(pad(x), w * scale[co]) for the output gradient dy, by float64 autograd; then (+ residual), ReLU, mask as above."""
+    x = torch.zeros(tuple(x_shape), dtype=D, requires_grad=True)
+    y = F.conv3d(_pad5(x, pf, pb), w.to(D), stride=tuple(stride))
+    g = dy.to(D)
+    y.backward(g * _chan(scale) if scale is not None else g)
+    return _epilogue(x.grad, residual, mask, relu)
+
+
+def conv_wgrad_ref64(x, dy, w_shape, stride, pf, pb):
+    """d(w) of y = conv3d(pad(x), w) for the output gradient dy, by float64 autograd."""
+    w = torch.zeros(tuple(w_shape), dtype=D, requires_grad=True)
+    F.conv3d(_pad5(x.to(D), pf, pb), w, stride=tuple(stride)).backward(dy.to(D))
+    return w.grad
+
+
+def conv_stats_ref64(z, groups=1):
+    """z (n, c, ...) -> (groups, 2, c): the sum and the sum of squares per channel over the pixels of each group of n / groups consecutive samples."""
+    n, c = z.shape[:2]
+    assert n % groups == 0
+    zz = z.to(D).reshape(groups, n // groups, c, -1)
+    return torch.stack([zz.sum((1, 3)), (zz * zz).sum((1, 3))], dim=1)
+
+
+def exact_in_fp32(*abs_sums, stats_z=None):
+    """The exactness gate: every argument is a compared quantity recomputed on ABSOLUTE values in float64 (sum |x||w|, sum |dy||x|, sum |z|, sum z^2).
+    All of them below 2^24 means that every partial sum the kernel can form, in any order, is an integer fp32 holds exactly. Where batch statistics are
+    compared, |z| < 4096 as well (z^2 < 2^24). A condition on the test's inputs, not a tolerance: a shape that breaks it needs sparser or smaller inputs."""
+    for a in abs_sums:
+        a = torch.as_tensor(a).to(D)
+        assert bool((a == a.round()).all()), "not integer-valued"
+        assert float(a.abs().max()) < 2.0 ** 24, float(a.abs().max())
+    if stats_z is not None:
+        assert float(torch.as_tensor(stats_z).abs().max()) < 4096.0
+    return True
+
+
+def round_once(t64, dtype):
+    """float64 -> fp32 (exact: checked) -> the 16-bit storage type, round-to-nearest-even; returned as float64."""
+    f = t64.to(torch.float32)
+    assert torch.equal(f.to(D), t64.to(D)), "not exact in fp32"
+    return f.to(TDT[dtype]).to(D)
+
+
+def first_mismatch(got, want):
+    """'' if equal, else the count of differing elements and the first differing index with both values (NaN == NaN, +0 == -0 do not count)."""
+    assert got.shape == want.shape, (got.shape, want.shape)
+    bad = (got != want) & ~(torch.isnan(got) & torch.isnan(want))
+    if not bool(bad.any()):
+        return ""
+    idx = tuple(int(i) for i in bad.nonzero()[0])
+    return "%d of %d differ; first at %s: got %r, want %r" % (int(bad.sum()), bad.numel(), idx, float(got[idx]), float(want[idx]))
+
+
+def wgrad_form(cin_k, cout8, k, stride, pf, in_thw, out_thw, n):
+    """The launch form tedspad_conv_wgrad picks (csrc/conv_wgrad.hip, the launcher's own formulas) and its number of pixel splits:
+    ('narrow' <1,4> | 'wide' <2,4> | '2x2' <2,2> | 'three' | 'patch', splits)."""
+    K = k[0] * k[1] * k[2] * cin_k
+    kpad = (K + 63) // 64 * 64
+    nkc = kpad // 64
+    M = n * out_thw[0] * out_thw[1] * out_thw[2]
+    narrow = (cout8 + 127) // 128 * 128 - cout8 >= 64
+    wide = (not narrow) and (nkc + 3) // 4 * 4 * 100 <= nkc * 115
+    if tuple(k) == (1, 3, 3) and tuple(stride) == (1, 1, 1) and tuple(pf) == (0, 1, 1) and tuple(out_thw) == tuple(in_thw) and cin_k % 64 == 0 and 9 * cin_k <= kpad:
+        tiles = (cin_k // 64) * ((cout8 + 63) // 64)
+        w, h = in_thw[2], in_thw[1]
+        tw, th = (w + 15) // 16, (h + 3) // 4
+        if tw * 16 * 100 <= w * 115 and w >= 14:
+            npatch = n * in_thw[0] * th * tw
+            sp = max(1, min((256 + tiles - 1) // tiles, (npatch + 7) // 8))
+            pps = (npatch + sp - 1) // sp
+            return "patch", (npatch + pps - 1) // pps
+        sp = max(1, min((256 + tiles - 1) // tiles, (M + 511) // 512))
+        rows = ((M + sp - 1) // sp + 63) // 64 * 64
+        return "three", (M + rows - 1) // rows
+    k_tiles = (nkc + 3) // 4 if (narrow or wide) else (nkc + 1) // 2
+    tiles = k_tiles * ((cout8 + 63) // 64 if narrow else (cout8 + 127) // 128)
+    sp = max(1, min((1024 + tiles - 1) // tiles, (M + 511) // 512))
+    rows = ((M + sp - 1) // sp + 63) // 64 * 64
+    return ("narrow" if narrow else "wide" if wide else "2x2"), (M + rows - 1) // rows
+
+
+def conv_out_dims(thw, k, stride, pf, pb):
+    return tuple((a + f + b - kk) // s + 1 for a, kk, s, f, b in zip(thw, k, stride, pf, pb))
+
+
+class ConvCase:
+    """One row of the case tables below: input dims (n, t, h, w), channels, kernel, stride, front / back pads (default: k // 2 both), the launch form of the
+    weight gradient the row is there for. `pair_w`: the stem in pixel-pair form (engine.stem_pair_form: 8 kernel channels = 2 pixels x 4, stride 1 along w)."""
+
+    def __init__(self, name, dims, cin, cout, k, stride=(1, 1, 1), pf=None, pb=None, form=None, multi_split=False, pair_w=None):
+        self.name, self.dims, self.cin, self.cout, self.k, self.stride = name, tuple(dims), cin, cout, tuple(k), tuple(stride)
+        self.pf = tuple(kk // 2 for kk in k) if pf is None else tuple(pf)
+        self.pb = self.pf if pb is None else tuple(pb)
+        self.form, self.multi_split, self.pair_w = form, multi_split, pair_w
+        self.out = conv_out_dims(self.dims[1:], self.k, self.stride, self.pf, self.pb)
+
+    def kernel_geometry(self):
+        """(cin_k, k, stride, pf, in_thw) as the kernels see the conv: the pixel-pair stem reads 8-channel pixel pairs with stride 1 along w."""
+        n, t, h, w = self.dims
+        if self.pair_w is None:
+            return (self.cin + 7) // 8 * 8, self.k, self.stride, self.pf, (t, h, w)
+        pw2 = (self.pair_w + 1) // 2
+        kw2 = (self.k[2] + 2 * pw2 - self.pair_w + 1) // 2
+        return 8, (self.k[0], self.k[1], kw2), (self.stride[0], self.stride[1], 1), (self.pf[0], self.pf[1], pw2), (t, h, w // 2)
+
+    def launch_form(self):
+        cin_k, k, stride, pf, thw = self.kernel_geometry()
+        return wgrad_form(cin_k, (self.cout + 7) // 8 * 8, k, stride, pf, thw, self.out, self.dims[0])
+
+    def tensors(self, seed=11, density=0.75):
+        """x, w, dy: small integers."""
+        n, t, h, w = self.dims
+        x = small_ints(seed, self.name + "x", (n, self.cin, t, h, w), density=density)
+        wt = small_ints(seed, self.name + "w", (self.cout, self.cin) + self.k, density=density)
+        dy = small_ints(seed, self.name + "dy", (n, self.cout) + self.out, density=density)
+        return x, wt, dy
+
+
+S2 = (1, 2, 2)
+WGRAD_POINTWISE = [
+    ConvCase("narrow_64_64", (2, 2, 9, 9), 64, 64, (1, 1, 1), form="narrow"),
+    ConvCase("narrow_64_40", (2, 2, 9, 9), 64, 40, (1, 1, 1), form="narrow"),
+    ConvCase("narrow_40_64", (2, 2, 9, 9), 40, 64, (1, 1, 1), form="narrow"),       # K = 40 < kpad = 64: padding columns
+    ConvCase("wide_256_128", (2, 2, 7, 9), 256, 128, (1, 1, 1), form="wide"),
+    ConvCase("2x2_192_128", (2, 2, 7, 9), 192, 128, (1, 1, 1), form="2x2"),
+    ConvCase("2x2_64_256", (2, 2, 7, 9), 64, 256, (1, 1, 1), form="2x2"),
+]
+WGRAD_THREE = [ConvCase("three_c%d_w%d_h%d" % (c, w, h), (n, t, h, w), c, 72, (1, 3, 3), form="three", multi_split=ms)
+               for c in (64, 128) for n, t, h, w, ms in ((2, 1, 9, 7, False), (2, 1, 9, 20, False), (1, 2, 3, 65, False), (2, 1, 30, 20, True))]
+WGRAD_PATCH = [ConvCase("patch_w%d_h%d" % (w, h), (1, 3, h, w), 128, 96, (1, 3, 3), form="patch") for w in (14, 16, 30, 63) for h in (5, 9)]
+GATHER_CASES = [       # the generic gather kernel (and the data gradient's strided cases)
+    ConvCase("t3_T2", (2, 2, 7, 9), 64, 128, (3, 1, 1), form="2x2"),
+    ConvCase("t3_T3", (2, 3, 7, 9), 128, 64, (3, 1, 1), form="narrow"),
+    ConvCase("s2_15", (2, 2, 15, 15), 64, 128, (1, 3, 3), S2, form="2x2"),
+    ConvCase("s2_14", (2, 1, 14, 14), 128, 128, (1, 3, 3), S2, form="wide"),
+    ConvCase("pw_s2", (2, 2, 15, 14), 64, 128, (1, 1, 1), S2, form="2x2"),
+    ConvCase("k333_s2_tfsame", (2, 4, 9, 9), 64, 64, (3, 3, 3), (2, 2, 2), pf=(0, 1, 1), pb=(1, 1, 1), form="narrow"),
+    ConvCase("stem_pair", (2, 8, 32, 32), 3, 64, (5, 7, 7), (2, 2, 2), pf=(2, 3, 3), form="narrow", pair_w=3),
+]
+WGRAD_CASES = WGRAD_POINTWISE + WGRAD_THREE + WGRAD_PATCH + GATHER_CASES
+DGRAD_CASES = GATHER_CASES + [
+    ConvCase("d_3x3", (2, 2, 12, 11), 64, 64, (1, 3, 3)),
+    ConvCase("d_1x1", (2, 2, 9, 9), 64, 256, (1, 1, 1)),
+]
+EPILOGUE_CASES = [     # PackedConv.__call__ under every tile configuration: dims, cin, cout, kernel, the configurations that must have run
+    (ConvCase("e_3x3_64_64", (6, 1, 20, 37), 64, 64, (1, 3, 3)), (5, 32, 33, 38, 40)),
+    (ConvCase("e_3x3_128_136", (3, 1, 33, 16), 128, 136, (1, 3, 3)), (5, 32, 33, 38)),
+    (ConvCase("e_1x1_64_128", (6, 2, 12, 12), 64, 128, (1, 1, 1)), (1, 5)),
+]
+EPILOGUE_GROUPS = 3
+
+
+def case_by_name(table, name):
+    return next(c for c in table if c.name == name)
+
+
+def epilogue_tensors(case, seed=17):
+    """x, w, bias, residual, mask for an EPILOGUE_CASES row: integers sparse enough that the sums of z and z^2 over all rows pass the gate."""
+    n, t, h, w = case.dims
+    x = small_ints(seed, case.name + "x", (n, case.cin, t, h, w), density=0.5)
+    wt = small_ints(seed, case.name + "w", (case.cout, case.cin) + case.k, density=0.5)
+    bias = small_ints(seed, case.name + "b", (case.cout,), density=1.0)
+    res = small_ints(seed, case.name + "r", (n, case.cout) + case.out, lo=-8, hi=8, density=1.0)
+    mask = signed_zero_mask(seed, case.name + "m", (n, case.cout) + case.out)
+    return x, wt, bias, res, mask
+
+
+def signed_zero_mask(seed, name, shape):
+    """Mask values drawn from {-1, -0.0, +0.0, 1}: only the last keeps the element (mask > 0)."""
+    u = synth_tensor(seed, name, shape).to(D)
+    return torch.tensor([-1.0, -0.0, 0.0, 1.0, 1.0, 1.0], dtype=D)[torch.floor(6.0 * u).long().clamp_(0, 5)]

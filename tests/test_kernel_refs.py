@@ -150,3 +150,109 @@ def test_loss_refs_vs_numpy_restatements():
     zi, zj = synth_tensor(2, "zi", (12, 64), -1, 1) * 0.3, synth_tensor(2, "zj", (12, 64), -1, 1) * 0.3
     for cos in (False, True):
         assert abs(float(R.ntxent_ref(zi, zj, 0.1, cos)[0]) - losses_ref.nt_xent_np(zi.numpy(), zj.numpy(), 0.1, use_cosine=cos)) < 1e-12 * max(1.0, abs(float(R.ntxent_ref(zi, zj, 0.1, cos)[0])))
+
+
+# ---- the exact-arithmetic conv references and the case tables of tests/test_hip_conv_exact.py ----------------------------------------------------------
+def _conv_taps(x, w, stride, pf, pb):
+    """conv3d as an explicit sum over taps of strided slices of the padded input: shares no code with F.conv3d."""
+    xp = F.pad(x, [pf[2], pb[2], pf[1], pb[1], pf[0], pb[0]])
+    co, ci, kt, kh, kw = w.shape
+    to, ho, wo = ((xp.shape[2 + i] - w.shape[2 + i]) // stride[i] + 1 for i in range(3))
+    y = torch.zeros((x.shape[0], co, to, ho, wo), dtype=D)
+    for dt in range(kt):
+        for dh in range(kh):
+            for dw in range(kw):
+                sl = xp[:, :, dt:dt + (to - 1) * stride[0] + 1:stride[0], dh:dh + (ho - 1) * stride[1] + 1:stride[1], dw:dw + (wo - 1) * stride[2] + 1:stride[2]]
+                y += torch.einsum("ncthw,oc->nothw", sl, w[:, :, dt, dh, dw])
+    return y
+
+
+CONV_REF_GEOS = [      # k, stride, front pad, back pad, (t, h, w)
+    ((1, 3, 3), (1, 1, 1), (0, 1, 1), (0, 1, 1), (2, 6, 7)),
+    ((3, 3, 3), (2, 2, 2), (0, 1, 1), (1, 1, 1), (4, 9, 9)),
+    ((1, 1, 1), (1, 2, 2), (0, 0, 0), (0, 0, 0), (2, 7, 6)),
+    ((5, 7, 7), (2, 2, 2), (2, 3, 3), (2, 3, 3), (4, 12, 10)),
+    ((3, 1, 1), (1, 1, 1), (1, 0, 0), (1, 0, 0), (3, 4, 5)),
+]
+
+
+@pytest.mark.parametrize("geo", CONV_REF_GEOS, ids=[str(g[0]) + str(g[1]) for g in CONV_REF_GEOS])
+def test_conv_refs_vs_float64_autograd(geo):
+    k, stride, pf, pb, thw = geo
+    n, ci, co = 2, 5, 6
+    x = synth_tensor(21, "x", (n, ci) + thw, -1, 1).to(D).requires_grad_()
+    w = synth_tensor(21, "w", (co, ci) + k, -1, 1).to(D).requires_grad_()
+    scale, shift = synth_tensor(21, "s", (co,), 0.5, 1.5).to(D), synth_tensor(21, "b", (co,), -1, 1).to(D)
+    z = _conv_taps(x, w * scale.view(-1, 1, 1, 1, 1), stride, pf, pb) + shift.view(1, -1, 1, 1, 1)
+    assert tuple(z.shape[2:]) == R.conv_out_dims(thw, k, stride, pf, pb)
+    res = synth_tensor(21, "r", tuple(z.shape), -1, 1).to(D)
+    mask = R.signed_zero_mask(21, "m", tuple(z.shape))
+    assert {float(v) for v in mask.unique()} == {-1.0, 0.0, 1.0} and bool(torch.signbit(mask[mask == 0]).any()) and not bool(torch.signbit(mask[mask == 0]).all())
+    y_ref, z_ref = R.conv_fwd_ref64(x.detach(), w.detach(), stride, pf, pb, scale=scale, shift=shift, residual=res, mask=mask, relu=True)
+    assert close(z_ref, z.detach()) and close(y_ref, (z.detach() + res).clamp_min(0) * (mask > 0))
+    dy = synth_tensor(21, "dy", tuple(z.shape), -1, 1).to(D)
+    z.backward(dy)
+    xres, xmask = synth_tensor(21, "xr", tuple(x.shape), -1, 1).to(D), R.signed_zero_mask(21, "xm", tuple(x.shape))
+    assert close(R.conv_dgrad_ref64(dy, w.detach(), x.shape, stride, pf, pb, scale=scale), x.grad)
+    assert close(R.conv_dgrad_ref64(dy, w.detach(), x.shape, stride, pf, pb, scale=scale, residual=xres, mask=xmask), (x.grad + xres) * (xmask > 0))
+    assert close(R.conv_wgrad_ref64(x.detach(), dy * scale.view(1, -1, 1, 1, 1), w.shape, stride, pf, pb), w.grad)
+    st = R.conv_stats_ref64(z.detach(), 2)
+    assert close(st[1, 0], z.detach()[1].sum((1, 2, 3))) and close(st[0, 1], (z.detach()[0] ** 2).sum((1, 2, 3))) and close(st.sum(0), R.conv_stats_ref64(z.detach())[0])
+
+
+def test_small_ints_round_once_and_the_gate():
+    v = R.small_ints(3, "v", (4096,), density=0.5)
+    assert set(v.tolist()) == {-2.0, -1.0, 0.0, 1.0, 2.0} and 0.55 < float((v == 0).double().mean()) < 0.65          # 0.5 + 0.5 / 5
+    for dt in (torch.float16, torch.bfloat16):
+        assert torch.equal(v.to(dt).to(D), v)
+    t = torch.tensor([257.0, 259.0, 2049.0, 131072.0, -3.0], dtype=D)
+    assert R.round_once(t, "bf16").tolist() == [256.0, 260.0, 2048.0, 131072.0, -3.0]                                # ties to even
+    assert R.round_once(t, "f16").tolist() == [257.0, 259.0, 2048.0, float("inf"), -3.0]
+    with pytest.raises(AssertionError):
+        R.round_once(torch.tensor([2.0 ** 24 + 1], dtype=D), "f16")
+    assert R.exact_in_fp32(torch.tensor([2.0 ** 24 - 1]))
+    for bad in (torch.tensor([2.0 ** 24]), torch.tensor([0.5])):
+        with pytest.raises(AssertionError):
+            R.exact_in_fp32(bad)
+    with pytest.raises(AssertionError):
+        R.exact_in_fp32(torch.tensor([1.0]), stats_z=torch.tensor([4096.0]))
+    assert R.first_mismatch(torch.tensor([1.0, 2.0]), torch.tensor([1.0, 2.0])) == "" and "first at (1,)" in R.first_mismatch(torch.tensor([1.0, 2.0]), torch.tensor([1.0, 3.0]))
+
+
+@pytest.mark.parametrize("case", R.WGRAD_CASES, ids=[c.name for c in R.WGRAD_CASES])
+def test_wgrad_case_table_reaches_its_form_and_passes_the_gate(case):
+    form, splits = case.launch_form()
+    assert form == case.form, (form, splits)
+    M = case.dims[0] * case.out[0] * case.out[1] * case.out[2]
+    if case.multi_split:
+        assert splits >= 3 and M % 64 != 0 and (M % (((M + splits - 1) // splits + 63) // 64 * 64)) % 64 != 0        # the last split ends inside a 64-pixel step
+    x, w, dy = case.tensors()
+    assert R.exact_in_fp32(R.conv_wgrad_ref64(x.abs(), dy.abs(), w.shape, case.stride, case.pf, case.pb) * 2)        # * 2: two accumulating calls
+    assert float(R.conv_wgrad_ref64(x, dy, w.shape, case.stride, case.pf, case.pb).abs().max()) > 0
+
+
+@pytest.mark.parametrize("case", R.DGRAD_CASES, ids=[c.name for c in R.DGRAD_CASES])
+def test_dgrad_case_table_passes_the_gate(case):
+    x, w, dy = case.tensors()
+    res = R.small_ints(11, case.name + "res", tuple(x.shape), lo=-8, hi=8, density=1.0)
+    assert R.exact_in_fp32(R.conv_dgrad_ref64(dy.abs(), w.abs(), x.shape, case.stride, case.pf, case.pb, scale=torch.full((case.cout,), 8.0)) + res.abs())
+    unread = R.conv_dgrad_ref64(torch.ones_like(dy), torch.ones_like(w), x.shape, case.stride, case.pf, case.pb) == 0
+    assert bool(unread.any()) == (case.name in ("pw_s2",)), case.name       # input positions the forward conv never reads
+
+
+@pytest.mark.parametrize("case,must", R.EPILOGUE_CASES, ids=[c.name for c, _ in R.EPILOGUE_CASES])
+def test_epilogue_case_table_passes_the_gate(case, must):
+    x, w, bias, res, mask = R.epilogue_tensors(case)
+    _, zabs = R.conv_fwd_ref64(x.abs(), w.abs(), case.stride, case.pf, case.pb, shift=bias.abs())
+    _, z = R.conv_fwd_ref64(x, w, case.stride, case.pf, case.pb, shift=bias)
+    st = R.conv_stats_ref64(z.abs(), 1)
+    assert R.exact_in_fp32(zabs + res.abs(), st[0, 0], st[0, 1], stats_z=zabs)
+    rows = case.dims[0] // R.EPILOGUE_GROUPS * case.out[0] * case.out[1] * case.out[2]
+    assert case.dims[0] % R.EPILOGUE_GROUPS == 0 and rows >= 256 and rows % 256 != 0              # group boundaries inside the 256-row tiles ...
+    assert rows % 64 != 0 or case.k == (1, 1, 1)                                                                  # ... and, for the 3 x 3 cases, inside the 64-row ones
+    assert 0.2 < float((mask > 0).double().mean()) < 0.8 and float(z.abs().max()) > 16
+
+
+def test_patch_cases_cover_one_split_and_several():
+    splits = {c.name: c.launch_form()[1] for c in R.WGRAD_PATCH}
+    assert min(splits.values()) == 1 and max(splits.values()) >= 3, splits
