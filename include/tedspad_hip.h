@@ -582,6 +582,49 @@ int32_t tedspad_mgfn_head(const float *x, int32_t ldx, int32_t M, int32_t C, con
 int32_t tedspad_mgfn_crop_mean(const float *a, float *a_out, const float *b, float *b_out, const int32_t *seg_off, int32_t nvid, int32_t tmax,
                                int32_t ncrops, void *stream);
 
+/* ---- validation of the action classifier, pictures of the anonymizer (csrc/action_eval.hip) -- all fp32, deterministic, no float atomics ---- */
+
+/* One validation batch behind the ft forward -- train_anonymizer.py:259,272,282-283 / train_anonymized_action.py:156,169,179-180:
+ * probs (B, C) = nn.functional.softmax(logits, dim=1) (max-subtracted), row_loss (B) = cross entropy per row, loss fp32[1] = their mean
+ * (nn.CrossEntropyLoss(), reduced in a fixed order), pred int32 (B) = np.flip(np.argsort(probs, axis=1), axis=1)[:, 0] with ties resolved
+ * as kind='stable' does: among exactly equal maxima the HIGHEST index (the reference's default sort kind leaves ties unspecified).
+ * labels: int64 (B) on the device; labels_host: the same values in host memory, range-checked before the launch, or NULL when the
+ * labels exist on the device only (a label outside [0, C) then gives a NaN row loss and reads nothing). One launch.
+ * 1 <= B <= 1024, 2 <= C <= 1024; anything else is TEDSPAD_EINVAL and nothing is launched. */
+int32_t tedspad_softmax_ce_eval(const float *logits, const int64_t *labels, const int64_t *labels_host, float *probs, float *row_loss,
+                                float *loss, int32_t *pred, int32_t B, int32_t C, void *stream);
+
+/* pred_dict[name].append(predictions[entry]) -- train_anonymizer.py:285-290 / train_anonymized_action.py:182-189, kept as running sums:
+ * sums[vid[b], :] += probs[b, :] and counts[vid[b]] += 1 for b = 0 .. B-1 IN ROW ORDER (two rows of a batch may name one video; the result
+ * does not depend on scheduling). sums fp32 (V, C), counts int32 (V). vid: int32 (B) on the device; vid_host: the same values in host
+ * memory -- an index outside [0, V) is TEDSPAD_EINVAL before anything is launched. One launch. */
+int32_t tedspad_vote_accumulate(const float *probs, const int32_t *vid, const int32_t *vid_host, float *sums, int32_t *counts, int32_t B,
+                                int32_t C, int32_t V, void *stream);
+
+/* predictions[entry] = np.mean(pred_dict[key], axis=0); c_pred = np.flip(np.argsort(predictions, axis=1), axis=1)[:, 0];
+ * c_pred == ground_truth -- train_anonymizer.py:475-487,491-504 / train_anonymized_action.py:352-364,368-381.
+ * mean (V, C) = sums / counts (IEEE division), pred_v int32 (V) with the tie rule above, correct uint8 (V) = (pred_v == labels_v), labels_v
+ * int64 (V). A video with counts == 0 was never seen: mean row 0, pred_v = -1, correct = 0. */
+int32_t tedspad_vote_finalize(const float *sums, const int32_t *counts, const int64_t *labels_v, float *mean, int32_t *pred_v,
+                              uint8_t *correct, int32_t V, int32_t C, void *stream);
+
+/* torchvision.utils.save_image(x, padding=pad, nrow=nrow) up to the file -- train_anonymizer.py:313-314. x: NCHW fp32 (N, 3, H, W), N >= 2;
+ * out: uint8 (Hg, Wg, 3). xmaps = min(nrow, N), ymaps = ceil(N / xmaps), Hg = ymaps (H + pad) + pad, Wg = xmaps (W + pad) + pad; image k
+ * starts at row (k / xmaps)(H + pad) + pad, column (k % xmaps)(W + pad) + pad; everything else is 0; each value is
+ * uint8(clamp(x * 255 + 0.5, 0, 255)), the multiply and the add rounded separately (torch's mul(255).add_(0.5)).
+ * tedspad_image_grid_dims (HOST side, pure CPU) gives Hg and Wg and makes the same argument checks. */
+int32_t tedspad_image_grid_dims(int32_t N, int32_t H, int32_t W, int32_t nrow, int32_t pad, int32_t *hg, int32_t *wg);
+int32_t tedspad_image_grid_u8(const float *x, uint8_t *out, int32_t N, int32_t H, int32_t W, int32_t nrow, int32_t pad, void *stream);
+
+/* save_video -- visualization/visualize_anonymization.py:52-59, after the colour flip of :108.
+ * tedspad_minmax_f32: out2 = {min, max} of n fp32 values (ws: fp32[tedspad_minmax_ws_floats()] workspace; two launches).
+ * tedspad_video_frames_u8: x (T, 3, H, W) fp32, minmax fp32[2] on the device -> out uint8 (T, H, W, 3) with the channel order reversed,
+ * uint8(trunc(((x - min) / (max - min)) * 255)): IEEE subtract, divide, multiply in that order, as numpy's fp32 does. max == min is 0 / 0 in
+ * the reference (undefined); here it writes zeros. */
+int32_t tedspad_minmax_ws_floats(void);
+int32_t tedspad_minmax_f32(const float *x, int64_t n, float *ws, float *out2, void *stream);
+int32_t tedspad_video_frames_u8(const float *x, const float *minmax, uint8_t *out, int32_t T, int32_t H, int32_t W, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

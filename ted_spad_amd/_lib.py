@@ -129,6 +129,14 @@ SYMBOLS = {
     "tedspad_mgfn_relpos": (_I32, [_P, _I32, _P, _I32, _I32, _I32, _P, _P, _P, _I32, _P]),
     "tedspad_mgfn_head": (_I32, [_P, _I32, _I32, _I32, _P, _P, _P, C.c_float, C.c_float, _P, _P, _P, _P, _P]),
     "tedspad_mgfn_crop_mean": (_I32, [_P, _P, _P, _P, _P, _I32, _I32, _I32, _P]),
+    "tedspad_softmax_ce_eval": (_I32, [_P] * 7 + [_I32, _I32, _P]),
+    "tedspad_vote_accumulate": (_I32, [_P] * 5 + [_I32, _I32, _I32, _P]),
+    "tedspad_vote_finalize": (_I32, [_P] * 6 + [_I32, _I32, _P]),
+    "tedspad_image_grid_dims": (_I32, [_I32] * 5 + [C.POINTER(_I32), C.POINTER(_I32)]),
+    "tedspad_image_grid_u8": (_I32, [_P, _P] + [_I32] * 5 + [_P]),
+    "tedspad_minmax_ws_floats": (_I32, []),
+    "tedspad_minmax_f32": (_I32, [_P, _I64, _P, _P, _P]),
+    "tedspad_video_frames_u8": (_I32, [_P, _P, _P, _I32, _I32, _I32, _P]),
 }
 
 _lib = None
