@@ -159,3 +159,5 @@ __device__ __forceinline__ int xcd_remap(int bid, int nwg) {
 }
 
 }  // namespace tedspad
+
+#include "launch.h"

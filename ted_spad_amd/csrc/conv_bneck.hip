@@ -853,17 +853,7 @@ int32_t launch_bneck128(const BneckKP &p, hipStream_t s) {
         set_error("tedspad_bneck_tail_fwd: halo does not fit LDS (%d bytes)", lds);
         return TEDSPAD_EINVAL;
     }
-    static thread_local int attr_set[2] = {0, 0};
-    auto kfn = conv_bneck_tail128_kernel<T>;
-    if (!attr_set[T::kDtype]) {
-        if (hipFuncSetAttribute((const void *)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) {
-            set_error("tedspad_bneck_tail_fwd: cannot raise the dynamic LDS limit");
-            return TEDSPAD_ELAUNCH;
-        }
-        attr_set[T::kDtype] = 1;
-    }
-    hipLaunchKernelGGL(kfn, dim3((p.M + BT_BM - 1) / BT_BM), dim3(256), lds, s, p);
-    return check_launch("tedspad_bneck_tail_fwd");
+    return launch_lds<conv_bneck_tail128_kernel<T>>("tedspad_bneck_tail_fwd", dim3((p.M + BT_BM - 1) / BT_BM), dim3(256), lds, s, p);
 }
 
 template <typename T, bool DUAL, bool POOLT = false>
@@ -878,18 +868,8 @@ int32_t launch_bneck(const BneckKP &p, hipStream_t s) {
         set_error("tedspad_bneck_tail_fwd: halo / conv3 weight image does not fit LDS (%d bytes)", lds);
         return TEDSPAD_EINVAL;
     }
-    static thread_local int attr_set[2] = {0, 0};
-    auto kfn = conv_bneck_tail_kernel<T, DUAL, POOLT>;
-    if (!attr_set[T::kDtype]) {
-        if (hipFuncSetAttribute((const void *)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) {
-            set_error("tedspad_bneck_tail_fwd: cannot raise the dynamic LDS limit");
-            return TEDSPAD_ELAUNCH;
-        }
-        attr_set[T::kDtype] = 1;
-    }
     const int tiles = POOLT ? (p.M / (2 * p.HW)) * p.tpf : (p.M + BT_BM - 1) / BT_BM;
-    hipLaunchKernelGGL(kfn, dim3(tiles), dim3(256), lds, s, p);
-    return check_launch("tedspad_bneck_tail_fwd");
+    return launch_lds<conv_bneck_tail_kernel<T, DUAL, POOLT>>("tedspad_bneck_tail_fwd", dim3(tiles), dim3(256), lds, s, p);
 }
 
 }  // namespace
@@ -929,16 +909,15 @@ extern "C" int32_t tedspad_bneck_tail_fwd(const tedspad_conv_desc *d2, const voi
     p.winv = ((1u << 20) + d2->w - 1) / d2->w; p.hinv = ((1u << 20) + d2->h - 1) / d2->h;
     p.R = d2->ph * d2->w + d2->pw; p.NP = BT_BM + (d2->kh - 1) * d2->w + (d2->kw - 1); p.ntaps = d2->kh * d2->kw;
     TS_REQUIRE(p.Kpad == p.ntaps * d2->cin, "tedspad_bneck_tail_fwd: unexpected K padding of the conv2 weights");
-    if (c128) return d2->dtype == TEDSPAD_F16 ? launch_bneck128<F16>(p, (hipStream_t)stream) : launch_bneck128<BF16>(p, (hipStream_t)stream);
+    if (c128) TS_WITH_T(d2->dtype, return launch_bneck128<T>(p, (hipStream_t)stream));
     p.HW = d2->h * d2->w; p.tpf = (p.HW + BT_BM - 1) / BT_BM;
     hipStream_t s = (hipStream_t)stream;
-    const bool f16 = d2->dtype == TEDSPAD_F16;
     if (variant & 4) {
         TS_REQUIRE(!x2 && d2->t % 2 == 0, "tedspad_bneck_tail_fwd: the temporal-pool variant takes the plain block (no second source) and an even frame count");
-        return f16 ? launch_bneck<F16, false, true>(p, s) : launch_bneck<BF16, false, true>(p, s);
+        TS_WITH_T(d2->dtype, return launch_bneck<T, false, true>(p, s));
     }
-    if (x2) return f16 ? launch_bneck<F16, true>(p, s) : launch_bneck<BF16, true>(p, s);
-    return f16 ? launch_bneck<F16, false>(p, s) : launch_bneck<BF16, false>(p, s);
+    if (x2) TS_WITH_T(d2->dtype, return launch_bneck<T, true>(p, s));
+    TS_WITH_T(d2->dtype, return launch_bneck<T, false>(p, s));
 }
 
 #ifdef TEDSPAD_BT_STAGE_STAMPS

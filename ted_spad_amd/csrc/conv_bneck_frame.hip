@@ -525,16 +525,5 @@ extern "C" int32_t tedspad_bneck_frame_fwd(const void *x, int32_t ldx, void *y, 
     p.scale1 = scale1; p.shift1 = shift1; p.scale2 = scale2; p.shift2 = shift2; p.scale3 = scale3; p.shift3 = shift3;
     p.frames = n * t; p.ldx = ldx; p.ldy = ldy; p.S1 = steps1; p.temporal = steps1 != cin / 32; p.relu = relu;
     hipStream_t s = (hipStream_t)stream;
-    static thread_local int attr_set[2] = {0, 0};
-    const void *kfn = dtype == TEDSPAD_F16 ? (const void *)bneck_frame_kernel<F16> : (const void *)bneck_frame_kernel<BF16>;
-    if (!attr_set[dtype]) {
-        if (hipFuncSetAttribute(kfn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) {
-            set_error("tedspad_bneck_frame_fwd: cannot raise the dynamic LDS limit");
-            return TEDSPAD_ELAUNCH;
-        }
-        attr_set[dtype] = 1;
-    }
-    if (dtype == TEDSPAD_F16) hipLaunchKernelGGL(bneck_frame_kernel<F16>, dim3(p.frames), dim3(512), BF_LDS, s, p);
-    else hipLaunchKernelGGL(bneck_frame_kernel<BF16>, dim3(p.frames), dim3(512), BF_LDS, s, p);
-    return check_launch("tedspad_bneck_frame_fwd");
+    TS_WITH_T(dtype, return launch_lds<bneck_frame_kernel<T>>("tedspad_bneck_frame_fwd", dim3(p.frames), dim3(512), BF_LDS, s, p));
 }

@@ -40,6 +40,20 @@ struct ConvKP {
     float sat;              // clamp of the f16 stores: 65504 (saturate), +inf on the training path (tedspad_conv_extras.nosat)
 };
 
+// Output channels [first, first + count) of a conv as a conv of its own: every per-channel pointer moves together (the launchers that run the last r <= 64 channels
+// of a cout = 128 k + r layer on a 64-wide tile, and the persistent two-patch kernel's halves)
+inline ConvKP cout_slice(const ConvKP &p, int first, int count) {
+    ConvKP q = p;
+    q.Cout = count;
+    q.w += (size_t)first * p.Kpad; q.scale += first; q.shift += first;
+    if (q.res) q.res += first;
+    if (q.y) q.y += first;
+    if (q.mask) q.mask += first;
+    if (q.stats) q.stats += first;
+    if (q.y32) q.y32 += first;
+    return q;
+}
+
 constexpr int BK = 64;                  // K elements per LDS tile row (8 chunks of 16 bytes)
 constexpr int KTAB_MAX_BYTES = 10240;   // Kpad <= 10240 (one int2 per 8 K elements)
 constexpr int KTAB_SMALL_BYTES = 1024;  // "short-K" configs: Kpad <= 1024, smaller LDS -> 2-3 workgroups per CU
@@ -63,8 +77,8 @@ struct PatchSrc {
     int ld[8];
     int up, n;
 };
-int32_t launch_conv_patch(int dtype, const ConvKP &p, int N, int cin, hipStream_t s, int mode = 0, const PatchSrc *src = nullptr);
-int32_t launch_conv_patch2(int dtype, const ConvKP &p, int N, int cin, hipStream_t s, const PatchSrc *src = nullptr, int flat = 0);   // tile_cfg 38 / 39: two patches (two flat tiles) per workgroup   // mode 1: tile_cfg 33 (256 consecutive pixels), 2: tile_cfg 34 (temporal)
+int32_t launch_conv_patch(int dtype, const ConvKP &p, int N, int cin, hipStream_t s, int mode = 0, const PatchSrc *src = nullptr);   // mode 1: tile_cfg 33 (256 consecutive pixels), 2: tile_cfg 34 (temporal)
+int32_t launch_conv_patch2(int dtype, const ConvKP &p, int N, int cin, hipStream_t s, const PatchSrc *src = nullptr);   // tile_cfg 38: two patches per workgroup
 
 // conv_patch3.hip: PERSISTENT two-patch kernel (tile_cfg 40): 8 waves, one workgroup per CU, halo double-buffered, weight ring of six stages (resident for cin <= 64),
 // epilogue straight from the accumulators; 1 x 3 x 3 'same' convs with 32 < cout <= 64

@@ -199,18 +199,8 @@ int32_t launch_flat_t(const ConvKP &p, hipStream_t s) {
         set_error("tedspad_conv_fwd: flat-halo config: halo does not fit LDS (%d bytes)", lds);
         return TEDSPAD_EINVAL;
     }
-    static thread_local int attr_set[2] = {0, 0};
-    auto kfn = conv_flat_kernel<T>;
-    if (!attr_set[T::kDtype]) {
-        if (hipFuncSetAttribute((const void *)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) {
-            set_error("tedspad_conv_fwd: cannot raise the dynamic LDS limit");
-            return TEDSPAD_ELAUNCH;
-        }
-        attr_set[T::kDtype] = 1;
-    }
     const int tiles = (p.M + FL_BM - 1) / FL_BM;
-    hipLaunchKernelGGL(kfn, dim3(tiles), dim3(256), lds, s, p, g);
-    return check_launch("tedspad_conv_fwd(flat halo)");
+    return launch_lds<conv_flat_kernel<T>>("tedspad_conv_fwd", "tedspad_conv_fwd(flat halo)", dim3(tiles), dim3(256), lds, s, p, g);
 }
 
 // ------------------------------------------------------------------------------------------------------------------------------
@@ -361,17 +351,7 @@ int32_t launch_tflat_t(const ConvKP &p, int N, int cin, hipStream_t s) {
     const int main_bytes = (256 + 8) * 128 + p.kt * FL_WSTAGE;
     const int stage_bytes = FL_BM * (64 + 4) * 4;
     const int lds = main_bytes > stage_bytes ? main_bytes : stage_bytes;
-    static thread_local int attr_set[2] = {0, 0};
-    auto kfn = conv_tflat_kernel<T_>;
-    if (!attr_set[T_::kDtype]) {
-        if (hipFuncSetAttribute((const void *)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) {
-            set_error("tedspad_conv_fwd: cannot raise the dynamic LDS limit");
-            return TEDSPAD_ELAUNCH;
-        }
-        attr_set[T_::kDtype] = 1;
-    }
-    hipLaunchKernelGGL(kfn, dim3(N * g.tiles_s), dim3(256), lds, s, p, g);
-    return check_launch("tedspad_conv_fwd(temporal flat halo)");
+    return launch_lds<conv_tflat_kernel<T_>>("tedspad_conv_fwd", "tedspad_conv_fwd(temporal flat halo)", dim3(N * g.tiles_s), dim3(256), lds, s, p, g);
 }
 
 }  // namespace
@@ -383,7 +363,7 @@ int32_t launch_conv_flat(int dtype, const ConvKP &p, int cin, hipStream_t s) {
         set_error("tedspad_conv_fwd: flat-halo config needs a stride-1 'same' 1 x kh x kw conv with cin = 64, cout <= 64 and the plain epilogue");
         return TEDSPAD_EINVAL;
     }
-    return dtype == TEDSPAD_F16 ? launch_flat_t<F16>(p, s) : launch_flat_t<BF16>(p, s);
+    TS_WITH_T(dtype, return launch_flat_t<T>(p, s));
 }
 
 }  // namespace tedspad
@@ -397,7 +377,7 @@ int32_t launch_conv_tflat(int dtype, const ConvKP &p, int N, int cin, hipStream_
         set_error("tedspad_conv_fwd: temporal flat-halo config needs a stride-1 'same' kt x 1 x 1 conv (kt 2..3) with cin %% 64 == 0, cout <= 64, T <= 4");
         return TEDSPAD_EINVAL;
     }
-    return dtype == TEDSPAD_F16 ? launch_tflat_t<F16>(p, N, cin, s) : launch_tflat_t<BF16>(p, N, cin, s);
+    TS_WITH_T(dtype, return launch_tflat_t<T>(p, N, cin, s));
 }
 
 }  // namespace tedspad

@@ -667,19 +667,9 @@ int32_t launch_stem_halo(const ConvKP &p, int N, hipStream_t s) {
         set_error("tedspad_conv_fwd: halo-direct config: halo does not fit LDS (%d bytes)", lds);
         return TEDSPAD_EINVAL;
     }
-    static thread_local int attr_set[2] = {0, 0};
-    auto kfn = conv_stem_halo_kernel<T, FR, KS, TW>;
-    if (attr_set[T::kDtype] < lds) {
-        if (hipFuncSetAttribute((const void *)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) {
-            set_error("tedspad_conv_fwd: cannot raise the dynamic LDS limit");
-            return TEDSPAD_ELAUNCH;
-        }
-        attr_set[T::kDtype] = 160 * 1024;
-    }
     const int tiles_h = (p.Ho + ST_TH - 1) / ST_TH, tiles_w = (p.Wo + ST_TW - 1) / ST_TW;
     const int tgroups = (p.To + FR - 1) / FR;
-    hipLaunchKernelGGL(kfn, dim3(N * tgroups * tiles_h * tiles_w), dim3(NT), lds, s, p, HH, WH, tiles_h, tiles_w);
-    return check_launch("tedspad_conv_fwd(halo)");
+    return launch_lds<conv_stem_halo_kernel<T, FR, KS, TW>>("tedspad_conv_fwd", "tedspad_conv_fwd(halo)", dim3(N * tgroups * tiles_h * tiles_w), dim3(NT), lds, s, p, HH, WH, tiles_h, tiles_w);
 }
 
 template <typename T, int BM, int BN, int WM, int WN, int S, int KT, int KS = 1>
@@ -743,7 +733,7 @@ inline long ntiles(const ConvKP &p, int bm, int bn) { return (long)((p.M + bm - 
 //      of 32 channels, a kernel row of weights per stage: a third fewer bytes through the LDS fill path than tile 32
 //  39  retired (the same on two flat tiles of 256 consecutive pixels: never picked)
 //  40  PERSISTENT two-patch kernel (conv_patch3.hip, round 6): tile 38's tile on 8 waves, one workgroup per CU walking a run of tiles; halo double-buffered (the next
-//      half chunk's / next tile's halo issued a half chunk ahead), weight ring of six stages filled five ahead -- resident when cin <= 64 --, epilogue straight from the
+//      half chunk's / next tile's halo issued a half chunk ahead), weight ring of six stages filled four ahead -- resident when cin <= 64 --, epilogue straight from the
 //      accumulators (v_permlane16_swap -> 16-byte pieces), batch statistics summed in registers over the whole run; 32 < cout <= 64; sums bit-identical to tile 38's
 constexpr int NUM_CFGS = 40;
 
@@ -773,16 +763,8 @@ int32_t launch_cfg(int cfg, const ConvKP &p, int N, int cin, hipStream_t s, cons
     const int sib = narrow_sibling(cfg);
     if (split_ok && sib && !src && p.Cout > 128 && p.Cout % 128 != 0 && p.Cout % 128 <= 64 && !p.fold_hw && !p.x2) {
         const int head = p.Cout / 128 * 128;
-        ConvKP a = p, b = p;
-        a.Cout = head;
-        b.Cout = p.Cout - head;
-        b.w += (size_t)head * p.Kpad; b.scale += head; b.shift += head;
-        if (b.res) b.res += head;
-        if (b.y) b.y += head;
-        if (b.mask) b.mask += head;
-        if (b.stats) b.stats += head;
-        if (b.y32) b.y32 += head;
-        if (launch_cfg<T>(sib, b, N, cin, s, nullptr) == TEDSPAD_OK) return launch_cfg<T>(cfg, a, N, cin, s, nullptr);
+        if (launch_cfg<T>(sib, cout_slice(p, head, p.Cout - head), N, cin, s, nullptr) == TEDSPAD_OK)
+            return launch_cfg<T>(cfg, cout_slice(p, 0, head), N, cin, s, nullptr);
     }
     switch (cfg) {
         case 9: return launch_stem_halo<T, 1, 1>(p, N, s);
@@ -1013,7 +995,7 @@ static int32_t conv_fwd_impl(const tedspad_conv_desc *d, const void *x, const vo
                    "tedspad_conv_fwd_ex: halo-direct tiles need statistics groups of whole samples");
     }
     const PatchSrc *gp = gathered ? &gsrc : nullptr;
-    return d->dtype == TEDSPAD_F16 ? launch_cfg<F16>(cfg, p, d->n, d->cin, s, gp) : launch_cfg<BF16>(cfg, p, d->n, d->cin, s, gp);
+    TS_WITH_T(d->dtype, return launch_cfg<T>(cfg, p, d->n, d->cin, s, gp));
 }
 
 extern "C" int32_t tedspad_conv_fwd_ex(const tedspad_conv_desc *d, const void *x, const void *w_packed, const int32_t *ktab,

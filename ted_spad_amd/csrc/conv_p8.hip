@@ -462,7 +462,7 @@ int32_t launch_conv_p8(int dtype, const ConvKP &p, hipStream_t s, int mf) {
         set_error("tedspad_conv_fwd: ping-pong config needs cin %% 64 == 0, K >= 128, cout %% 256 == 0 and the plain epilogue");
         return TEDSPAD_EINVAL;
     }
-    return dtype == TEDSPAD_F16 ? launch_p8<F16>(p, s, mf) : launch_p8<BF16>(p, s, mf);
+    TS_WITH_T(dtype, return launch_p8<T>(p, s, mf));
 }
 
 }  // namespace tedspad

@@ -7,16 +7,19 @@
 // not an MFMA overlaps the MFMAs while the two waves of a SIMD run the same program in the same phase. So here, all together:
 //   * ONE 8-wave workgroup per CU, persistent over a contiguous run of tiles; a tile = two consecutive 16 x 16 patches x 64 output channels. Waves 0-3 (group 0)
 //     own patch 0, waves 4-7 (group 1) patch 1; a wave owns 4 rows x 64 channels (16 accumulator quads of v_mfma_f32_16x16x32).
-//   * PING-PONG (the structure of conv_p8.hip): a PHASE is one tap (dw) of one kernel row (dh) of one 32-channel half chunk: a LOAD segment (the tap's 8 fragment
-//     reads, at most one or two LDS-DMA instructions, one piece of the previous tile's epilogue) and a COMPUTE segment (16 MFMAs), each ended by a raw
-//     s_barrier; group 1 runs one segment behind group 0, so while one wave of a SIMD multiplies, its partner reads, issues DMA and converts / stores.
-//   * the halo of a half chunk lives in a ring of 2 (weights resident) or 3 (weights streamed) buffers of 41 KB and is fetched one / two half chunks ahead, ONE
-//     DMA instruction per wave and phase (an LDS-DMA instruction holds its wave for its whole queueing time: a burst of 41 behind one barrier cost 340 us of the
-//     2 377 us the lockstep form took on 320 -> 64);
-//   * weights: cin <= 64 (at most six stages of [3 taps][64 co][32 k]): fetched ONCE per workgroup, resident for all of its tiles; otherwise a ring of nine
-//     4 KB tap units, unit n + 8 issued in phase n by waves 0-3 (one instruction each);
-//   * the epilogue straight from the accumulators, piece by piece in the load segments of the NEXT tile's first eight phases (two accumulator sets take turns):
-//     v_permlane16_swap turns the 16 x 16 x 32 accumulator quads (4 channels = 8 bytes per lane) into 16-byte pieces, 64 contiguous bytes per pixel and store;
+//   * PING-PONG (the structure of conv_p8.hip): a PHASE is one kernel row (dh) of one 32-channel half chunk = one weight stage: a LOAD segment (this phase's LDS-DMA
+//     instructions, at a tile's first phase the previous tile's epilogue, the fragment reads of the row's first two taps) and a COMPUTE segment (3 x 16 MFMAs, the
+//     third tap's fragments read behind the first tap's MFMAs), each ended by a raw s_barrier; group 1 runs one segment behind group 0, so while one wave of a
+//     SIMD multiplies, its partner reads, issues DMA and converts / stores.
+//   * the halo of a half chunk lives in one of TWO buffers of 42 KB (hb, flipped with `hb ^= 1` after every half chunk): while buffer hb is multiplied, the halo of the
+//     next half chunk -- or of the next tile's first -- goes into buffer hb ^ 1 in the half chunk's first two phases, 3 (4) + 2 instructions per wave, a group
+//     fetching its own patch (an LDS-DMA instruction holds its wave for its whole queueing time: a burst of 41 behind one barrier cost 340 us of the 2 377 us the
+//     lockstep form took on 320 -> 64);
+//   * weights: P3_NWS = 6 slots of one stage [3 taps][64 co][32 k] (12 KB). cin <= 64 (at most six stages): fetched ONCE per workgroup in the prologue, resident for
+//     all of its tiles (RES). Otherwise a ring: stages 0..3 in the prologue, then stage n + 4 is issued in phase n -- FOUR stages ahead -- into slot (n + 4) % 6,
+//     which held stage n - 2; the groups take turns (group (n + 4) & 1 issues it, three instructions per wave);
+//   * the epilogue straight from the accumulators, in the load segment of the NEXT tile's first phase (beside the other group's MFMAs): v_permlane16_swap turns
+//     the 16 x 16 x 32 accumulator quads (4 channels = 8 bytes per lane) into 16-byte pieces, 64 contiguous bytes per pixel and store;
 //   * the training extras from registers as well: batch statistics are summed per lane over ALL tiles of the workgroup and flushed once (2 atomic
 //     instructions per wave instead of 128 atomics per patch), fp32 output, ReLU-backward mask, residual.
 //   * LOADER WAVES for the streamed-weight inference variants (template flag LDR): waves 8..11 issue every LDS-DMA instruction and do the counted waits, on the same phase
@@ -24,10 +27,22 @@
 // K is walked (half chunk, dh, dw) exactly as tile 38 does: the sums are bit-identical to tile 38's.
 //
 // Ordering argument (segments are the barrier-delimited intervals; group 0 runs LOAD of phase n in segment 2n and COMPUTE in 2n + 1, group 1 one segment later; every
-// LOAD segment ends with lgkmcnt(0) in front of its barrier, every COMPUTE segment with the counted vmcnt wait in front of its barrier):
-//   RAW  bytes read in phase n were waited for -- by the wave that asked for them -- in phase <= n - 2, i.e. before the barrier that ends segment 2 (n - 2) + 2 = 2n - 2;
-//        the earliest read of them is issued in segment 2n;
-//   WAR  the fragment reads of phase k have returned by the end of segment 2k + 1; a DMA into their bytes is issued in phase >= k + 1, i.e. in segment >= 2k + 2.
+// LOAD segment ends with lgkmcnt(0) in front of its barrier, every COMPUTE segment with lgkmcnt(0) in front of its last tap and the counted vmcnt wait in front of its
+// barrier; a wave waits only for DMA it issued itself, the barrier behind the wait publishes it):
+//   weights, RAW  stage k is issued in phase k - 4 by group k & 1 and has been waited for by that group when its COMPUTE segment of phase k - 2 ends (the phase-2 wait
+//                 leaves only the youngest stage in flight, the phase-0 / 1 waits count down to stage n + 2): segment 2k - 3 or 2k - 2. Its first read is group 0's LOAD
+//                 of phase k, segment 2k.
+//   weights, WAR  the slot of stage n + 4 held stage n - 2, whose last reads (the third tap's fragments) have returned when the COMPUTE segment of phase n - 2 ends: segment
+//                 2n - 3 (group 0) or 2n - 2 (group 1). Stage n + 4 is issued in the LOAD segment of phase n: segment 2n or 2n + 1.
+//   halo, RAW     a group reads only its own patch's half of a buffer and fetched it itself: the pieces issued in the first two phases of a half chunk are waited for in the
+//                 COMPUTE segment of its third phase (everything but the youngest weight stage has landed) and read from the group's next LOAD segment on, one barrier later.
+//   halo, WAR     buffer hb ^ 1 was last read in the third phase of the half chunk before, by this group; those reads returned before the barrier that ends that COMPUTE
+//                 segment, and the first DMA into the buffer is issued in the group's next LOAD segment.
+//   RES           the prologue ends with vmcnt(0) and a barrier and no weight slot is written again: only the halo lines apply (the third phase waits with vmcnt(0)).
+//   LDR           the loader waves run group 0's segments: stage n + 4 in segment 2n (its slot's last reads, group 1's COMPUTE of phase n - 2, ended with segment 2n - 2),
+//                 the halo pieces of BOTH patches in segment 2n + 1 of a half chunk's first two phases (buffer hb ^ 1's last reads, group 1's COMPUTE of the phase before,
+//                 ended with segment 2n), then the counted wait: stage n + 1 and, in the third phase, the whole next halo have landed when segment 2n + 1 ends; group 0
+//                 reads them from segment 2n + 2 on.
 #include "conv_common.h"
 
 namespace tedspad {
@@ -48,7 +63,7 @@ constexpr int P3_HG = 21 * 1024;                                                
 constexpr int P3_HALO = 2 * P3_HG;                                                  // 43 008: both patches
 constexpr int P3_WST = 3 * 64 * 64;                                                 // a weight stage [3 dw][64 co][32 k]: 12 288 bytes
 constexpr int P3_WTAP = 64 * 64;
-constexpr int P3_NWS = 6;                                                           // weight stages in LDS: all of them when cin <= 64, otherwise a ring filled five stages ahead
+constexpr int P3_NWS = 6;                                                           // weight stages in LDS: all of them when cin <= 64, otherwise a ring filled four stages ahead (stage n + 4 issued in phase n)
 constexpr int P3_WBASE = 2 * P3_HALO;
 constexpr int P3_SCB = P3_WBASE + P3_NWS * P3_WST;                                  // scale[64] | shift[64]
 constexpr int P3_LDS = P3_SCB + 512;                                                // 160 256
@@ -77,25 +92,6 @@ __device__ __forceinline__ void swap16(uint32_t &x, uint32_t &y) {      // rows 
 template <typename T>
 __device__ __forceinline__ uint32_t pack2_lim(float a, float b, float lim) {
     return (uint32_t)T::from_f32_lim(a, lim) | ((uint32_t)T::from_f32_lim(b, lim) << 16);
-}
-
-// a tile's two patches: first row / column, frame, presence
-struct P3Tile {
-    int pf[2], ph0[2], pw0[2];
-    bool pon[2];
-};
-
-__device__ __forceinline__ P3Tile p3_decode(int tile, const Patch3Geo &g) {
-    P3Tile t;
-#pragma unroll
-    for (int q = 0; q < 2; ++q) {
-        int pi = 2 * tile + q;
-        t.pon[q] = pi < g.npatch;
-        if (!t.pon[q]) pi = 2 * tile;
-        const int tw = pi % g.tiles_w, t2 = pi / g.tiles_w;
-        t.pw0[q] = tw * P3_S; t.ph0[q] = (t2 % g.tiles_h) * P3_S; t.pf[q] = t2 / g.tiles_h;
-    }
-    return t;
 }
 
 #define P3_SEG_END()                          \
@@ -615,19 +611,9 @@ int32_t launch_patch3_t(const ConvKP &p, int frames, int cin, hipStream_t s, con
     const int nwg_env = nwg_s ? atoi(nwg_s) : 0;
     int grid = nwg_env > 0 ? nwg_env : g_p3_cus;
     if (grid > g.ntiles) grid = g.ntiles;
-    static thread_local int attr_set[2] = {0, 0};
-    auto kfn = conv_patch3_kernel<T, SRC, STATS, RES, GEN, LDR>;
-    if (!attr_set[T::kDtype]) {
-        if (hipFuncSetAttribute((const void *)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) {
-            set_error("tedspad_conv_fwd: cannot raise the dynamic LDS limit");
-            return TEDSPAD_ELAUNCH;
-        }
-        attr_set[T::kDtype] = 1;
-    }
     PatchSrc gsrc{};
     if (SRC) gsrc = *src;
-    hipLaunchKernelGGL(kfn, dim3(grid), dim3(LDR ? P3_NTL : P3_NT), P3_LDS, s, p, g, gsrc);
-    return check_launch("tedspad_conv_fwd(persistent two-patch halo)");
+    return launch_lds<conv_patch3_kernel<T, SRC, STATS, RES, GEN, LDR>>("tedspad_conv_fwd", "tedspad_conv_fwd(persistent two-patch halo)", dim3(grid), dim3(LDR ? P3_NTL : P3_NT), P3_LDS, s, p, g, gsrc);
 }
 
 }  // namespace
@@ -642,17 +628,7 @@ int32_t launch_conv_patch3(int dtype, const ConvKP &p, int N, int cin, hipStream
     static const bool split128 = getenv("TEDSPAD_P3_NO_128") == nullptr;          // A/B knob
     if (p.Cout != 128 || !split128) return launch_conv_patch3_64(dtype, p, N, cin, s, src);
     for (int half = 0; half < 2; ++half) {
-        ConvKP q = p;
-        const int o = 64 * half;
-        q.Cout = 64;
-        q.w = p.w + (size_t)o * p.Kpad;
-        q.scale = p.scale + o; q.shift = p.shift + o;
-        if (p.y) q.y = p.y + o;
-        if (p.y32) q.y32 = p.y32 + o;
-        if (p.res) q.res = p.res + o;
-        if (p.mask) q.mask = p.mask + o;
-        if (p.stats) q.stats = p.stats + o;
-        const int32_t rc = launch_conv_patch3_64(dtype, q, N, cin, s, src);
+        const int32_t rc = launch_conv_patch3_64(dtype, cout_slice(p, 64 * half, 64), N, cin, s, src);
         if (rc != TEDSPAD_OK) return rc;          // (the first launch declines before anything is written: the conditions do not depend on the half)
     }
     return TEDSPAD_OK;

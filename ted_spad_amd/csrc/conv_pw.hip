@@ -296,9 +296,9 @@ int32_t launch_conv_pw(int dtype, const ConvKP &p, hipStream_t s, bool pool_t) {
         set_error("tedspad_conv_pool_t2_fwd: needs at least two frames");
         return TEDSPAD_EINVAL;
     }
-    if (p.x2) return dtype == TEDSPAD_F16 ? launch_pw<F16, 2>(p, false, s) : launch_pw<BF16, 2>(p, false, s);
-    if (p.cin == 64) return dtype == TEDSPAD_F16 ? launch_pw<F16, 1>(p, pool_t, s) : launch_pw<BF16, 1>(p, pool_t, s);
-    return dtype == TEDSPAD_F16 ? launch_pw<F16, 2>(p, pool_t, s) : launch_pw<BF16, 2>(p, pool_t, s);
+    if (p.x2) TS_WITH_T(dtype, return launch_pw<T, 2>(p, false, s));
+    if (p.cin == 64) TS_WITH_T(dtype, return launch_pw<T, 1>(p, pool_t, s));
+    TS_WITH_T(dtype, return launch_pw<T, 2>(p, pool_t, s));
 }
 
 }  // namespace tedspad

@@ -875,17 +875,21 @@ extern "C" int32_t tedspad_clip_to_tp(const float *x, void *y, int32_t n, int32_
     const dim3 g((unsigned)((long)n * h * wtiles));
     hipStream_t s = (hipStream_t)stream;
     if (w % 4 == 0 && ((uintptr_t)x | (uintptr_t)(sn * 4) | (uintptr_t)(sc * 4) | (uintptr_t)(st * 4) | (uintptr_t)(sh * 4)) % 16 == 0) {
-        if (dtype == TEDSPAD_F16) hipLaunchKernelGGL(clip_to_tp4_kernel<F16>, g, dim3(256), 0, s, x, (uint16_t *)y, c, t, h, w, (long)sn, (long)sc, (long)st, (long)sh, pad_t, stride_t, t_pairs, wtiles);
-        else hipLaunchKernelGGL(clip_to_tp4_kernel<BF16>, g, dim3(256), 0, s, x, (uint16_t *)y, c, t, h, w, (long)sn, (long)sc, (long)st, (long)sh, pad_t, stride_t, t_pairs, wtiles);
+        TS_LAUNCH_T(dtype, clip_to_tp4_kernel<T>, g, dim3(256), 0, s, x, (uint16_t *)y, c, t, h, w, (long)sn, (long)sc, (long)st, (long)sh, pad_t, stride_t, t_pairs, wtiles);
         return check_launch("tedspad_clip_to_tp");
     }
-    if (dtype == TEDSPAD_F16) hipLaunchKernelGGL(clip_to_tp_kernel<F16>, g, dim3(256), 0, s, x, (uint16_t *)y, c, t, h, w, (long)sn, (long)sc, (long)st, (long)sh, pad_t, stride_t, t_pairs, wtiles);
-    else hipLaunchKernelGGL(clip_to_tp_kernel<BF16>, g, dim3(256), 0, s, x, (uint16_t *)y, c, t, h, w, (long)sn, (long)sc, (long)st, (long)sh, pad_t, stride_t, t_pairs, wtiles);
+    TS_LAUNCH_T(dtype, clip_to_tp_kernel<T>, g, dim3(256), 0, s, x, (uint16_t *)y, c, t, h, w, (long)sn, (long)sc, (long)st, (long)sh, pad_t, stride_t, t_pairs, wtiles);
     return check_launch("tedspad_clip_to_tp");
 }
 
 extern "C" int32_t tedspad_stem_pt_wimg_bytes(void) { return PT_W_BYTES; }
 extern "C" int32_t tedspad_stem_pt_wimg16_bytes(void) { return PT_W16_BYTES; }
+
+// A/B knob, read once: 0 = the 8-wave forms without loader waves (8 loader waves measured the same as 4 on the tap-pair form)
+static bool stem_loaders() {
+    static const bool lw = getenv("TEDSPAD_STEM_LOADERS") == nullptr || atoi(getenv("TEDSPAD_STEM_LOADERS")) != 0;
+    return lw;
+}
 
 // shared launcher: pool = the spatial 3x3 / 2 max-pool fused as well (y is the pooled tensor then, side its scratch)
 static int32_t stem_pt_launch(const char *who, const void *x_tp, const void *w_img, const float *scale, const float *shift, void *y, void *side, int32_t n,
@@ -909,76 +913,30 @@ static int32_t stem_pt_launch(const char *who, const void *x_tp, const void *w_i
     int grid = nwg > 0 ? nwg : 256;
     grid = (grid + 7) / 8 * 8;
     if ((long)grid > total + 7) grid = (int)((total + 7) / 8 * 8);
-    static thread_local int attr_set[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     const int w8 = (variant >> 1) & 1;
     p.dbg = (variant >> 8) & 15;
-    if (direct) {                          // the same form reading the fp32 clip itself
-        static const bool lw = getenv("TEDSPAD_STEM_LOADERS") == nullptr || atoi(getenv("TEDSPAD_STEM_LOADERS")) != 0;       // A/B knob: 0 = the 8-wave form
-        static thread_local int attrd[4] = {0, 0, 0, 0};
-        const int ti = (dtype == TEDSPAD_F16 ? 0 : 1) + (lw ? 2 : 0);
-        const void *fnd = ti == 0 ? (const void *)conv_stem_pt_kernel<F16, 8, true, 16, true> : ti == 1 ? (const void *)conv_stem_pt_kernel<BF16, 8, true, 16, true>
-                        : ti == 2 ? (const void *)conv_stem_pt_kernel<F16, 8, true, 16, true, 8> : (const void *)conv_stem_pt_kernel<BF16, 8, true, 16, true, 8>;
-        if (!attrd[ti]) {
-            if (hipFuncSetAttribute(fnd, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) {
-                set_error("%s: cannot raise the dynamic LDS limit", who);
-                return TEDSPAD_ELAUNCH;
-            }
-            attrd[ti] = 1;
-        }
-        if (ti == 0) hipLaunchKernelGGL((conv_stem_pt_kernel<F16, 8, true, 16, true>), dim3(grid), dim3(512), pt_lds_pool(16), s, p);
-        else if (ti == 1) hipLaunchKernelGGL((conv_stem_pt_kernel<BF16, 8, true, 16, true>), dim3(grid), dim3(512), pt_lds_pool(16), s, p);
-        else if (ti == 2) hipLaunchKernelGGL((conv_stem_pt_kernel<F16, 8, true, 16, true, 8>), dim3(grid), dim3(1024), pt_lds_pool(16), s, p);
-        else hipLaunchKernelGGL((conv_stem_pt_kernel<BF16, 8, true, 16, true, 8>), dim3(grid), dim3(1024), pt_lds_pool(16), s, p);
+    // every form below: <MFMA waves, pool fused, MFMA shape (32 / 16), fp32 clip read directly, loader waves>; the block holds the MFMA waves and the loader waves
+    int32_t rc;
+#define STEM_PT(BLOCK, LDS, ...) TS_WITH_T(dtype, rc = launch_lds<conv_stem_pt_kernel<T, __VA_ARGS__>>(who, dim3(grid), dim3(BLOCK), LDS, s, p))
+    if (direct) {                                 // the 16x16x32 form reading the fp32 clip itself
+        if (stem_loaders()) STEM_PT(1024, pt_lds_pool(16), 8, true, 16, true, 8);
+        else STEM_PT(512, pt_lds_pool(16), 8, true, 16, true);
     } else if (pool && (variant & 4)) {           // 16x16x32 MFMA form (8 waves; w_img in the tap-pair layout), by default with 4 loader waves issuing its halo DMA
-        static const bool lw = getenv("TEDSPAD_STEM_LOADERS") == nullptr || atoi(getenv("TEDSPAD_STEM_LOADERS")) != 0;       // A/B knob: 0 = the 8-wave form (8 loader waves measured the same as 4)
-        static thread_local int attr16[4] = {0, 0, 0, 0};
-        const int ti = (dtype == TEDSPAD_F16 ? 0 : 1) + (lw ? 2 : 0);
-        const void *fn16 = ti == 0 ? (const void *)conv_stem_pt_kernel<F16, 8, true, 16> : ti == 1 ? (const void *)conv_stem_pt_kernel<BF16, 8, true, 16>
-                         : ti == 2 ? (const void *)conv_stem_pt_kernel<F16, 8, true, 16, false, 4> : (const void *)conv_stem_pt_kernel<BF16, 8, true, 16, false, 4>;
-        if (!attr16[ti]) {
-            if (hipFuncSetAttribute(fn16, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) {
-                set_error("%s: cannot raise the dynamic LDS limit", who);
-                return TEDSPAD_ELAUNCH;
-            }
-            attr16[ti] = 1;
-        }
-        if (ti == 0) hipLaunchKernelGGL((conv_stem_pt_kernel<F16, 8, true, 16>), dim3(grid), dim3(512), pt_lds_pool(16), s, p);
-        else if (ti == 1) hipLaunchKernelGGL((conv_stem_pt_kernel<BF16, 8, true, 16>), dim3(grid), dim3(512), pt_lds_pool(16), s, p);
-        else if (ti == 2) hipLaunchKernelGGL((conv_stem_pt_kernel<F16, 8, true, 16, false, 4>), dim3(grid), dim3(768), pt_lds_pool(16), s, p);
-        else hipLaunchKernelGGL((conv_stem_pt_kernel<BF16, 8, true, 16, false, 4>), dim3(grid), dim3(768), pt_lds_pool(16), s, p);
+        if (stem_loaders()) STEM_PT(768, pt_lds_pool(16), 8, true, 16, false, 4);
+        else STEM_PT(512, pt_lds_pool(16), 8, true, 16);
+    } else if (w8) {
+        if (pool) STEM_PT(512, PT_LDS_POOL, 8, true);
+        else STEM_PT(512, PT_LDS, 8, false);
     } else {
-    const int di = ((dtype == TEDSPAD_F16 ? 0 : 1) * 2 + w8) * 2 + (pool ? 1 : 0);
-    const void *fns[8] = {(const void *)conv_stem_pt_kernel<F16, 4, false>, (const void *)conv_stem_pt_kernel<F16, 4, true>,
-                          (const void *)conv_stem_pt_kernel<F16, 8, false>, (const void *)conv_stem_pt_kernel<F16, 8, true>,
-                          (const void *)conv_stem_pt_kernel<BF16, 4, false>, (const void *)conv_stem_pt_kernel<BF16, 4, true>,
-                          (const void *)conv_stem_pt_kernel<BF16, 8, false>, (const void *)conv_stem_pt_kernel<BF16, 8, true>};
-    if (!attr_set[di]) {
-        if (hipFuncSetAttribute(fns[di], hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) {
-            set_error("%s: cannot raise the dynamic LDS limit", who);
-            return TEDSPAD_ELAUNCH;
-        }
-        attr_set[di] = 1;
+        if (pool) STEM_PT(256, PT_LDS_POOL, 4, true);
+        else STEM_PT(256, PT_LDS, 4, false);
     }
-    const dim3 g(grid), b(w8 ? 512 : 256);
-    const int lds = pool ? PT_LDS_POOL : PT_LDS;
-    switch (di) {
-        case 0: hipLaunchKernelGGL((conv_stem_pt_kernel<F16, 4, false>), g, b, lds, s, p); break;
-        case 1: hipLaunchKernelGGL((conv_stem_pt_kernel<F16, 4, true>), g, b, lds, s, p); break;
-        case 2: hipLaunchKernelGGL((conv_stem_pt_kernel<F16, 8, false>), g, b, lds, s, p); break;
-        case 3: hipLaunchKernelGGL((conv_stem_pt_kernel<F16, 8, true>), g, b, lds, s, p); break;
-        case 4: hipLaunchKernelGGL((conv_stem_pt_kernel<BF16, 4, false>), g, b, lds, s, p); break;
-        case 5: hipLaunchKernelGGL((conv_stem_pt_kernel<BF16, 4, true>), g, b, lds, s, p); break;
-        case 6: hipLaunchKernelGGL((conv_stem_pt_kernel<BF16, 8, false>), g, b, lds, s, p); break;
-        default: hipLaunchKernelGGL((conv_stem_pt_kernel<BF16, 8, true>), g, b, lds, s, p); break;
-    }
-    }
-    int32_t rc = check_launch(who);
+#undef STEM_PT
     if (rc != TEDSPAD_OK || !pool || p.tiles_w < 2) return rc;
     const long rows = (long)n * t_pairs * hp;
     const long pieces = rows * (p.tiles_w - 1) * 8;
     const dim3 fg((unsigned)((pieces + 255) / 256));
-    if (dtype == TEDSPAD_F16) hipLaunchKernelGGL(stem_pool_fix_kernel<F16>, fg, dim3(256), 0, s, (uint16_t *)y, (const uint16_t *)side, rows, wp, p.tiles_w, ldy);
-    else hipLaunchKernelGGL(stem_pool_fix_kernel<BF16>, fg, dim3(256), 0, s, (uint16_t *)y, (const uint16_t *)side, rows, wp, p.tiles_w, ldy);
+    TS_LAUNCH_T(dtype, stem_pool_fix_kernel<T>, fg, dim3(256), 0, s, (uint16_t *)y, (const uint16_t *)side, rows, wp, p.tiles_w, ldy);
     return check_launch(who);
 }
 

@@ -306,7 +306,6 @@ extern "C" int32_t tedspad_unetpp_tail_fwd(const void *x, int32_t ldx, float *y,
     UppTailKP p;
     p.x = (const uint16_t *)x; p.wimg = (const uint16_t *)w_img; p.sc1 = scale1; p.sh1 = shift1; p.sc2 = scale2; p.sh2 = shift2; p.b3 = bias3; p.y = y;
     p.ldx = ldx; p.N = n; p.H = h; p.W = w; p.tiles_h = (h + 15) / 16; p.tiles_w = (w + 15) / 16; p.npatch = n * p.tiles_h * p.tiles_w;
-    static thread_local int attr_set[2] = {0, 0};
     static thread_local int ncu = 0;
     if (!ncu) {
         int dev = 0;
@@ -318,26 +317,5 @@ extern "C" int32_t tedspad_unetpp_tail_fwd(const void *x, int32_t ldx, float *y,
         ncu = prop.multiProcessorCount;
     }
     const int grid = p.npatch < ncu ? p.npatch : ncu;
-    if (dtype == TEDSPAD_F16) {
-        auto kfn = unetpp_tail_kernel<F16>;
-        if (!attr_set[0]) {
-            if (hipFuncSetAttribute((const void *)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) {
-                set_error("tedspad_unetpp_tail_fwd: cannot raise the dynamic LDS limit");
-                return TEDSPAD_ELAUNCH;
-            }
-            attr_set[0] = 1;
-        }
-        hipLaunchKernelGGL(kfn, dim3(grid), dim3(512), UT_LDS, (hipStream_t)stream, p);
-    } else {
-        auto kfn = unetpp_tail_kernel<BF16>;
-        if (!attr_set[1]) {
-            if (hipFuncSetAttribute((const void *)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) {
-                set_error("tedspad_unetpp_tail_fwd: cannot raise the dynamic LDS limit");
-                return TEDSPAD_ELAUNCH;
-            }
-            attr_set[1] = 1;
-        }
-        hipLaunchKernelGGL(kfn, dim3(grid), dim3(512), UT_LDS, (hipStream_t)stream, p);
-    }
-    return check_launch("tedspad_unetpp_tail_fwd");
+    TS_WITH_T(dtype, return launch_lds<unetpp_tail_kernel<T>>("tedspad_unetpp_tail_fwd", dim3(grid), dim3(512), UT_LDS, (hipStream_t)stream, p));
 }

@@ -668,32 +668,12 @@ extern "C" int32_t tedspad_conv_wgrad(const tedspad_conv_desc *d, const void *x,
             // TEDSPAD_WGRAD3P_LOADERS = 0: without the loader waves (A/B knob). Measured and not kept (profiles/r06_ab_experiments.md): 2 loaders (half the gain), 6 (= 4),
             // rings of 4 / 5 slots (= 3), the two compute groups a barrier segment apart (slower), an LDS-counter hand-over instead of the barrier (slower)
             static const bool ld3p = getenv("TEDSPAD_WGRAD3P_LOADERS") == nullptr || atoi(getenv("TEDSPAD_WGRAD3P_LOADERS")) != 0;
-            const int form = ld3p ? 1 : 0;
-            static thread_local int attr3p[4] = {0, 0, 0, 0};
-            const bool h16 = d->dtype == TEDSPAD_F16;
-            const int ti = form * 2 + (h16 ? 0 : 1);
-#define W3P_FN(N) (h16 ? (const void *)conv_wgrad3p_kernel<F16, N, 3> : (const void *)conv_wgrad3p_kernel<BF16, N, 3>)
-            const void *fn = form == 0 ? W3P_FN(0) : W3P_FN(4);
-#undef W3P_FN
-            const int ring = 3;
-            if (!attr3p[ti]) {
-                if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) {
-                    set_error("tedspad_conv_wgrad: cannot raise the dynamic LDS limit");
-                    return TEDSPAD_ELAUNCH;
-                }
-                attr3p[ti] = 1;
-            }
             const dim3 gridp((unsigned)(tiles3 * sp));
-            const int nthr = form == 0 ? 384 : 640;
-            void *kargs[2] = {(void *)&p, (void *)&g3};
-            if (hipLaunchKernel(fn, gridp, dim3(nthr), kargs, ring * (form == 0 ? W3P_STAGE0 : W3P_STAGE), s) != hipSuccess) {
-                set_error("tedspad_conv_wgrad: launch failed");
-                return TEDSPAD_ELAUNCH;
-            }
-            return check_launch("tedspad_conv_wgrad");
+            const char *who = "tedspad_conv_wgrad";      // <loader waves, ring slots>: 6 compute waves and the loader waves
+            if (ld3p) TS_WITH_T(d->dtype, return launch_lds<conv_wgrad3p_kernel<T, 4, 3>>(who, gridp, dim3(640), 3 * W3P_STAGE, s, p, g3));
+            TS_WITH_T(d->dtype, return launch_lds<conv_wgrad3p_kernel<T, 0, 3>>(who, gridp, dim3(384), 3 * W3P_STAGE0, s, p, g3));
         }
-        if (d->dtype == TEDSPAD_F16) hipLaunchKernelGGL((conv_wgrad3_kernel<F16>), grid3, dim3(384), 0, s, p);
-        else hipLaunchKernelGGL((conv_wgrad3_kernel<BF16>), grid3, dim3(384), 0, s, p);
+        TS_LAUNCH_T(d->dtype, (conv_wgrad3_kernel<T>), grid3, dim3(384), 0, s, p);
         return check_launch("tedspad_conv_wgrad");
     }
     // split the pixels so the grid covers the chip ~4x, each split a whole number of 64-pixel steps (>= 8 steps)
@@ -708,14 +688,11 @@ extern "C" int32_t tedspad_conv_wgrad(const tedspad_conv_desc *d, const void *x,
     p.rows_per_split = (int)rows;
     const dim3 grid((unsigned)(tiles * splits));
     if (narrow) {
-        if (d->dtype == TEDSPAD_F16) hipLaunchKernelGGL((conv_wgrad_kernel<F16, 1, 4>), grid, dim3(256), 0, s, p);
-        else hipLaunchKernelGGL((conv_wgrad_kernel<BF16, 1, 4>), grid, dim3(256), 0, s, p);
+        TS_LAUNCH_T(d->dtype, (conv_wgrad_kernel<T, 1, 4>), grid, dim3(256), 0, s, p);
     } else if (wide) {
-        if (d->dtype == TEDSPAD_F16) hipLaunchKernelGGL((conv_wgrad_kernel<F16, 2, 4>), grid, dim3(512), 0, s, p);
-        else hipLaunchKernelGGL((conv_wgrad_kernel<BF16, 2, 4>), grid, dim3(512), 0, s, p);
+        TS_LAUNCH_T(d->dtype, (conv_wgrad_kernel<T, 2, 4>), grid, dim3(512), 0, s, p);
     } else {
-        if (d->dtype == TEDSPAD_F16) hipLaunchKernelGGL((conv_wgrad_kernel<F16, 2, 2>), grid, dim3(256), 0, s, p);
-        else hipLaunchKernelGGL((conv_wgrad_kernel<BF16, 2, 2>), grid, dim3(256), 0, s, p);
+        TS_LAUNCH_T(d->dtype, (conv_wgrad_kernel<T, 2, 2>), grid, dim3(256), 0, s, p);
     }
     return check_launch("tedspad_conv_wgrad");
 }

@@ -413,27 +413,9 @@ extern "C" int32_t tedspad_frames_crop_resize_tp(const void *frames, int32_t in_
     q.in_end = (const uint8_t *)frames + (size_t)T * H * W * C * (in_is_float ? 4 : 1);
     hipStream_t s = (hipStream_t)stream;
     const dim3 g((unsigned)((long)n_clips * oh * (t_pairs + 1)));
-    if (lds > 64 * 1024) {                       // wide source frames (HD): raise the kernel's dynamic LDS limit once per variant
-        static thread_local bool raised[4] = {false, false, false, false};
-        const int vi = (in_is_float ? 2 : 0) + (dtype == TEDSPAD_F16 ? 0 : 1);
-        if (!raised[vi]) {
-            const void *fn = vi == 0 ? (const void *)crop_resize_tp_kernel<uint8_t, F16> : vi == 1 ? (const void *)crop_resize_tp_kernel<uint8_t, BF16> :
-                             vi == 2 ? (const void *)crop_resize_tp_kernel<float, F16> : (const void *)crop_resize_tp_kernel<float, BF16>;
-            if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) {
-                set_error("tedspad_frames_crop_resize_tp: cannot raise the dynamic LDS limit");
-                return TEDSPAD_ELAUNCH;
-            }
-            raised[vi] = true;
-        }
-    }
-    if (in_is_float) {
-        if (dtype == TEDSPAD_F16) hipLaunchKernelGGL((crop_resize_tp_kernel<float, F16>), g, dim3(256), lds, s, q);
-        else hipLaunchKernelGGL((crop_resize_tp_kernel<float, BF16>), g, dim3(256), lds, s, q);
-    } else {
-        if (dtype == TEDSPAD_F16) hipLaunchKernelGGL((crop_resize_tp_kernel<uint8_t, F16>), g, dim3(256), lds, s, q);
-        else hipLaunchKernelGGL((crop_resize_tp_kernel<uint8_t, BF16>), g, dim3(256), lds, s, q);
-    }
-    return check_launch("tedspad_frames_crop_resize_tp");
+    const char *who = "tedspad_frames_crop_resize_tp";      // (wide source frames (HD) need more than the default 64 KB of dynamic LDS)
+    if (in_is_float) TS_WITH_T(dtype, return launch_lds<crop_resize_tp_kernel<float, T>>(who, g, dim3(256), lds, s, q));
+    TS_WITH_T(dtype, return launch_lds<crop_resize_tp_kernel<uint8_t, T>>(who, g, dim3(256), lds, s, q));
 }
 
 extern "C" int32_t tedspad_segment_pool_mag(const float *feat, int32_t T, int32_t ncrops, int32_t F, int32_t length, float *out,

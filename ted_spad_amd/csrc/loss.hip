@@ -182,16 +182,7 @@ extern "C" int32_t tedspad_ntxent_fwd_bwd(const float *zis, const float *zjs, fl
     TS_REQUIRE(2 * N <= NTX_MAX_ROWS && C <= NTX_MAX_C && C % 2 == 0,
                "tedspad_ntxent_fwd_bwd: supports 2N <= 64 and even C <= 256 (reference: N=12, C=128)");
     const size_t lds = (size_t)(2 * NTX_MAX_ROWS * (C + 1) + NTX_MAX_ROWS * 65 + NTX_MAX_ROWS + 4) * sizeof(float);
-    static thread_local bool attr = false;
-    if (!attr) {
-        if (hipFuncSetAttribute((const void *)ntxent_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) {
-            set_error("tedspad_ntxent_fwd_bwd: cannot raise the dynamic LDS limit");
-            return TEDSPAD_ELAUNCH;
-        }
-        attr = true;
-    }
-    hipLaunchKernelGGL(ntxent_kernel, dim3(1), dim3(256), lds, (hipStream_t)stream, zis, zjs, loss, dzis, dzjs, N, C, 1.f / temperature, use_cosine);
-    return check_launch("tedspad_ntxent_fwd_bwd");
+    return launch_lds<ntxent_kernel>("tedspad_ntxent_fwd_bwd", dim3(1), dim3(256), lds, (hipStream_t)stream, zis, zjs, loss, dzis, dzjs, N, C, 1.f / temperature, use_cosine);
 }
 
 extern "C" int32_t tedspad_triplet_fwd_bwd(const float *a, const float *p, const float *n, float *loss, float *row_ws, float *da,

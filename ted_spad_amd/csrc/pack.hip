@@ -310,8 +310,7 @@ extern "C" int32_t tedspad_pack_conv_weights(const float *w, const float *scale,
     const long chunks = (long)rows_pad * (kpad / 8);
     long g = (chunks + 255) / 256; if (g > 4096) g = 4096;
     hipStream_t s = (hipStream_t)stream;
-    if (dtype == TEDSPAD_F16) hipLaunchKernelGGL(pack_kernel<F16>, dim3((unsigned)g), dim3(256), 0, s, p);
-    else hipLaunchKernelGGL(pack_kernel<BF16>, dim3((unsigned)g), dim3(256), 0, s, p);
+    TS_LAUNCH_T(dtype, pack_kernel<T>, dim3((unsigned)g), dim3(256), 0, s, p);
     return check_launch("tedspad_pack_conv_weights");
 }
 

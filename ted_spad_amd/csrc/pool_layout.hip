@@ -459,12 +459,6 @@ __global__ __launch_bounds__(256) void upsample2x_kernel(const uint16_t *x, uint
     }
 }
 
-inline int grid_for(long work_items) {
-    long g = (work_items + 255) / 256;
-    if (g > 256 * 16) g = 256 * 16;  // grid-stride the rest
-    return g < 1 ? 1 : (int)g;
-}
-
 // F.interpolate(scale_factor=2, mode="nearest") of smp's DecoderBlock (segmentation_models_pytorch 0.3.3, decoders/unetplusplus/decoder.py:
 // DecoderBlock.forward), written into its channel slice of the block's concat buffer; also the plain channel-slice copy that places a
 // tensor the UNet++ dense skip pathway concatenates twice. 16 bytes (8 channels) per thread, dtype-agnostic.
@@ -569,8 +563,7 @@ extern "C" int32_t tedspad_count_saturated(const void *x, int64_t rows, int32_t 
     if (rows == 0) return TEDSPAD_OK;
     const long total = rows * (c / 8);
     const int grid = (int)(total / 256 + 1 < 2048 ? total / 256 + 1 : 2048);
-    if (dtype == TEDSPAD_F16) hipLaunchKernelGGL((count_saturated_kernel<F16>), dim3(grid), dim3(256), 0, (hipStream_t)stream, (const uint4 *)x, (long)rows, c / 8, ldx / 8, out2);
-    else hipLaunchKernelGGL((count_saturated_kernel<BF16>), dim3(grid), dim3(256), 0, (hipStream_t)stream, (const uint4 *)x, (long)rows, c / 8, ldx / 8, out2);
+    TS_LAUNCH_T(dtype, (count_saturated_kernel<T>), dim3(grid), dim3(256), 0, (hipStream_t)stream, (const uint4 *)x, (long)rows, c / 8, ldx / 8, out2);
     return check_launch("tedspad_count_saturated");
 }
 
@@ -620,19 +613,7 @@ extern "C" int32_t tedspad_maxpool_fwd_idx(const tedspad_pool_desc *d, const voi
             if (lds_ok && fits) {
                 const uint32_t ninf2 = d->dtype == TEDSPAD_F16 ? 0xFC00FC00u : 0xFF80FF80u;
                 const uint32_t padw2 = d->pad_zero ? 0u : ninf2;
-                static thread_local int attr_k3[2] = {0, 0};
-                const int ti = d->dtype == TEDSPAD_F16 ? 0 : 1;
-                if (!attr_k3[ti]) {
-                    const void *fn = ti == 0 ? (const void *)maxpool_k3s1_lds_kernel<F16> : (const void *)maxpool_k3s1_lds_kernel<BF16>;
-                    if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) {
-                        set_error("tedspad_maxpool_fwd: cannot raise the dynamic LDS limit");
-                        return TEDSPAD_ELAUNCH;
-                    }
-                    attr_k3[ti] = 1;
-                }
-                if (ti == 0) hipLaunchKernelGGL(maxpool_k3s1_lds_kernel<F16>, dim3((unsigned)wgs), dim3(256), (size_t)lds, s, p.x, p.y, d->t, d->h, d->w, p.C8, p.ldx, p.ldy, padw2, g);
-                else hipLaunchKernelGGL(maxpool_k3s1_lds_kernel<BF16>, dim3((unsigned)wgs), dim3(256), (size_t)lds, s, p.x, p.y, d->t, d->h, d->w, p.C8, p.ldx, p.ldy, padw2, g);
-                return check_launch("tedspad_maxpool_fwd");
+                TS_WITH_T(d->dtype, return launch_lds<maxpool_k3s1_lds_kernel<T>>("tedspad_maxpool_fwd", dim3((unsigned)wgs), dim3(256), (size_t)lds, s, p.x, p.y, d->t, d->h, d->w, p.C8, p.ldx, p.ldy, padw2, g));
             }
         }
         long rows = (long)d->n * d->t * ((d->h + 1) / 2) * p.C8;
@@ -643,17 +624,14 @@ extern "C" int32_t tedspad_maxpool_fwd_idx(const tedspad_pool_desc *d, const voi
         // a row whose window is entirely padding cannot occur (pad 1 < 3), so with "skip" semantics -inf never survives
         const uint32_t ninf = d->dtype == TEDSPAD_F16 ? 0xFC00FC00u : 0xFF80FF80u;
         const uint32_t padw = d->pad_zero ? 0u : ninf;
-        if (d->dtype == TEDSPAD_F16) hipLaunchKernelGGL(maxpool_k3s1_kernel<F16>, dim3(grid_for(tot)), dim3(256), 0, s, p.x, p.y, d->n, d->t, d->h, d->w, p.C8, p.ldx, p.ldy, padw, segs, seglen, tot);
-        else hipLaunchKernelGGL(maxpool_k3s1_kernel<BF16>, dim3(grid_for(tot)), dim3(256), 0, s, p.x, p.y, d->n, d->t, d->h, d->w, p.C8, p.ldx, p.ldy, padw, segs, seglen, tot);
+        TS_LAUNCH_T(d->dtype, maxpool_k3s1_kernel<T>, dim3(grid_for(tot)), dim3(256), 0, s, p.x, p.y, d->n, d->t, d->h, d->w, p.C8, p.ldx, p.ldy, padw, segs, seglen, tot);
         return check_launch("tedspad_maxpool_fwd");
     }
     if (!idx) {
-        if (d->dtype == TEDSPAD_F16) hipLaunchKernelGGL(maxpool_noidx_kernel<F16>, dim3(grid_for(p.total)), dim3(256), 0, s, p, 0xFC00FC00u);
-        else hipLaunchKernelGGL(maxpool_noidx_kernel<BF16>, dim3(grid_for(p.total)), dim3(256), 0, s, p, 0xFF80FF80u);
+        TS_LAUNCH_T(d->dtype, maxpool_noidx_kernel<T>, dim3(grid_for(p.total)), dim3(256), 0, s, p, d->dtype == TEDSPAD_F16 ? 0xFC00FC00u : 0xFF80FF80u);
         return check_launch("tedspad_maxpool_fwd");
     }
-    if (d->dtype == TEDSPAD_F16) hipLaunchKernelGGL(maxpool_kernel<F16>, dim3(grid_for(p.total)), dim3(256), 0, s, p);
-    else hipLaunchKernelGGL(maxpool_kernel<BF16>, dim3(grid_for(p.total)), dim3(256), 0, s, p);
+    TS_LAUNCH_T(d->dtype, maxpool_kernel<T>, dim3(grid_for(p.total)), dim3(256), 0, s, p);
     return check_launch("tedspad_maxpool_fwd");
 }
 
@@ -664,8 +642,7 @@ extern "C" int32_t tedspad_global_avgpool_fwd(const void *x, float *y, int32_t n
     TS_REQUIRE(dtype == TEDSPAD_F16 || dtype == TEDSPAD_BF16, "tedspad_global_avgpool_fwd: bad dtype");
     const int blocks = n * ((c / 8 + 63) / 64);
     hipStream_t s = (hipStream_t)stream;
-    if (dtype == TEDSPAD_F16) hipLaunchKernelGGL(avgpool_kernel<F16>, dim3(blocks), dim3(256), 0, s, (const uint16_t *)x, y, n, spatial, c / 8, ldx);
-    else hipLaunchKernelGGL(avgpool_kernel<BF16>, dim3(blocks), dim3(256), 0, s, (const uint16_t *)x, y, n, spatial, c / 8, ldx);
+    TS_LAUNCH_T(dtype, avgpool_kernel<T>, dim3(blocks), dim3(256), 0, s, (const uint16_t *)x, y, n, spatial, c / 8, ldx);
     return check_launch("tedspad_global_avgpool_fwd");
 }
 
@@ -683,16 +660,13 @@ extern "C" int32_t tedspad_clip_to_channels_last(const float *x, void *y, int32_
         const long tot = (long)n * t * h * (w / 8);
         const dim3 g(grid_for(tot));
         if (cpad == 4) {
-            if (dtype == TEDSPAD_F16) hipLaunchKernelGGL((to_channels_last_w8_kernel<F16, 4>), g, dim3(256), 0, s, x, (uint16_t *)y, c, t, h, w / 8, (long)sn, (long)sc, (long)st_, (long)sh, tot);
-            else hipLaunchKernelGGL((to_channels_last_w8_kernel<BF16, 4>), g, dim3(256), 0, s, x, (uint16_t *)y, c, t, h, w / 8, (long)sn, (long)sc, (long)st_, (long)sh, tot);
+            TS_LAUNCH_T(dtype, (to_channels_last_w8_kernel<T, 4>), g, dim3(256), 0, s, x, (uint16_t *)y, c, t, h, w / 8, (long)sn, (long)sc, (long)st_, (long)sh, tot);
         } else {
-            if (dtype == TEDSPAD_F16) hipLaunchKernelGGL((to_channels_last_w8_kernel<F16, 8>), g, dim3(256), 0, s, x, (uint16_t *)y, c, t, h, w / 8, (long)sn, (long)sc, (long)st_, (long)sh, tot);
-            else hipLaunchKernelGGL((to_channels_last_w8_kernel<BF16, 8>), g, dim3(256), 0, s, x, (uint16_t *)y, c, t, h, w / 8, (long)sn, (long)sc, (long)st_, (long)sh, tot);
+            TS_LAUNCH_T(dtype, (to_channels_last_w8_kernel<T, 8>), g, dim3(256), 0, s, x, (uint16_t *)y, c, t, h, w / 8, (long)sn, (long)sc, (long)st_, (long)sh, tot);
         }
         return check_launch("tedspad_clip_to_channels_last");
     }
-    if (dtype == TEDSPAD_F16) hipLaunchKernelGGL(to_channels_last_kernel<F16>, dim3(grid_for(total8)), dim3(256), 0, s, x, (uint16_t *)y, c, t, h, w, (long)sn, (long)sc, (long)st_, (long)sh, (long)sw, cpad, total8);
-    else hipLaunchKernelGGL(to_channels_last_kernel<BF16>, dim3(grid_for(total8)), dim3(256), 0, s, x, (uint16_t *)y, c, t, h, w, (long)sn, (long)sc, (long)st_, (long)sh, (long)sw, cpad, total8);
+    TS_LAUNCH_T(dtype, to_channels_last_kernel<T>, dim3(grid_for(total8)), dim3(256), 0, s, x, (uint16_t *)y, c, t, h, w, (long)sn, (long)sc, (long)st_, (long)sh, (long)sw, cpad, total8);
     return check_launch("tedspad_clip_to_channels_last");
 }
 
@@ -702,8 +676,7 @@ extern "C" int32_t tedspad_channels_last_to_nchw(const void *x, float *y, int32_
     TS_REQUIRE(dtype == TEDSPAD_F16 || dtype == TEDSPAD_BF16, "tedspad_channels_last_to_nchw: bad dtype");
     const long thw = (long)t * h * w, total = (long)n * c * thw;
     hipStream_t s = (hipStream_t)stream;
-    if (dtype == TEDSPAD_F16) hipLaunchKernelGGL(to_nchw_kernel<F16>, dim3(grid_for(total)), dim3(256), 0, s, (const uint16_t *)x, y, c, thw, ldx, total);
-    else hipLaunchKernelGGL(to_nchw_kernel<BF16>, dim3(grid_for(total)), dim3(256), 0, s, (const uint16_t *)x, y, c, thw, ldx, total);
+    TS_LAUNCH_T(dtype, to_nchw_kernel<T>, dim3(grid_for(total)), dim3(256), 0, s, (const uint16_t *)x, y, c, thw, ldx, total);
     return check_launch("tedspad_channels_last_to_nchw");
 }
 
@@ -718,8 +691,7 @@ extern "C" int32_t tedspad_upsample_bilinear2x_fwd(const void *x, void *y, int32
     TS_REQUIRE(dtype == TEDSPAD_F16 || dtype == TEDSPAD_BF16, "tedspad_upsample_bilinear2x_fwd: bad dtype");
     const long total = (long)n * ho * wo * (c / 8);
     hipStream_t s = (hipStream_t)stream;
-    if (dtype == TEDSPAD_F16) hipLaunchKernelGGL(upsample2x_kernel<F16>, dim3(grid_for(total)), dim3(256), 0, s, (const uint16_t *)x, (uint16_t *)y, h, w, c / 8, ldx, ldy, ho, wo, pad_top, pad_left, total);
-    else hipLaunchKernelGGL(upsample2x_kernel<BF16>, dim3(grid_for(total)), dim3(256), 0, s, (const uint16_t *)x, (uint16_t *)y, h, w, c / 8, ldx, ldy, ho, wo, pad_top, pad_left, total);
+    TS_LAUNCH_T(dtype, upsample2x_kernel<T>, dim3(grid_for(total)), dim3(256), 0, s, (const uint16_t *)x, (uint16_t *)y, h, w, c / 8, ldx, ldy, ho, wo, pad_top, pad_left, total);
     return check_launch("tedspad_upsample_bilinear2x_fwd");
 }
 
@@ -750,8 +722,7 @@ extern "C" int32_t tedspad_upsample_nearest2x_bwd(const void *dy, void *dx, int3
     TS_REQUIRE(dtype == TEDSPAD_F16 || dtype == TEDSPAD_BF16, "tedspad_upsample_nearest2x_bwd: bad dtype");
     const long total = (long)n * h * w * (c / 8);
     hipStream_t s = (hipStream_t)stream;
-    if (dtype == TEDSPAD_F16) hipLaunchKernelGGL(upsample_nearest2x_bwd_kernel<F16>, dim3(grid_for(total)), dim3(256), 0, s, (const uint4 *)dy, (uint4 *)dx, h, w, c / 8, ldy / 8, ldx / 8, accumulate, total);
-    else hipLaunchKernelGGL(upsample_nearest2x_bwd_kernel<BF16>, dim3(grid_for(total)), dim3(256), 0, s, (const uint4 *)dy, (uint4 *)dx, h, w, c / 8, ldy / 8, ldx / 8, accumulate, total);
+    TS_LAUNCH_T(dtype, upsample_nearest2x_bwd_kernel<T>, dim3(grid_for(total)), dim3(256), 0, s, (const uint4 *)dy, (uint4 *)dx, h, w, c / 8, ldy / 8, ldx / 8, accumulate, total);
     return check_launch("tedspad_upsample_nearest2x_bwd");
 }
 
@@ -761,8 +732,7 @@ extern "C" int32_t tedspad_add_channels(const void *x, void *y, int64_t npix, in
     TS_REQUIRE(dtype == TEDSPAD_F16 || dtype == TEDSPAD_BF16, "tedspad_add_channels: bad dtype");
     const long total = (long)npix * (c / 8);
     hipStream_t s = (hipStream_t)stream;
-    if (dtype == TEDSPAD_F16) hipLaunchKernelGGL(add_channels_kernel<F16>, dim3(grid_for(total)), dim3(256), 0, s, (const uint4 *)x, (uint4 *)y, c / 8, ldx / 8, ldy / 8, total);
-    else hipLaunchKernelGGL(add_channels_kernel<BF16>, dim3(grid_for(total)), dim3(256), 0, s, (const uint4 *)x, (uint4 *)y, c / 8, ldx / 8, ldy / 8, total);
+    TS_LAUNCH_T(dtype, add_channels_kernel<T>, dim3(grid_for(total)), dim3(256), 0, s, (const uint4 *)x, (uint4 *)y, c / 8, ldx / 8, ldy / 8, total);
     return check_launch("tedspad_add_channels");
 }
 
@@ -775,7 +745,6 @@ extern "C" int32_t tedspad_avgpool3d_s1_fwd(const void *x, float *y, int32_t n, 
     const int to = t - kt + 1, ho = h - kh + 1, wo = w - kw + 1;
     const long total = (long)n * to * ho * wo * (c / 8);
     hipStream_t s = (hipStream_t)stream;
-    if (dtype == TEDSPAD_F16) hipLaunchKernelGGL(avgpool3d_s1_kernel<F16>, dim3(grid_for(total)), dim3(256), 0, s, (const uint16_t *)x, y, t, h, w, c / 8, ldx, kt, kh, kw, to, ho, wo, total);
-    else hipLaunchKernelGGL(avgpool3d_s1_kernel<BF16>, dim3(grid_for(total)), dim3(256), 0, s, (const uint16_t *)x, y, t, h, w, c / 8, ldx, kt, kh, kw, to, ho, wo, total);
+    TS_LAUNCH_T(dtype, avgpool3d_s1_kernel<T>, dim3(grid_for(total)), dim3(256), 0, s, (const uint16_t *)x, y, t, h, w, c / 8, ldx, kt, kh, kw, to, ho, wo, total);
     return check_launch("tedspad_avgpool3d_s1_fwd");
 }

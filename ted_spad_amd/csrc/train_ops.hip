@@ -15,12 +15,6 @@
 namespace tedspad {
 namespace {
 
-inline int grid_for(long items) {
-    long g = (items + 255) / 256;
-    if (g > 256 * 16) g = 256 * 16;
-    return g < 1 ? 1 : (int)g;
-}
-
 // grid for kernels that set up per-channel terms once per thread (bn_train_apply: 8 divisions, 8 rsqrt and 32 loads for 8 channels): `iters`
 // items per thread where the tensor allows it, but never fewer than ~2 workgroups per CU
 inline int grid_for_iters(long items, int iters) {
@@ -673,11 +667,6 @@ using namespace tedspad;
 
 #define TS_DT(code) ((code) == TEDSPAD_F16 || (code) == TEDSPAD_BF16)
 #define TS_ZDT(zcode, code, ldz) ((zcode) == TEDSPAD_F32 || ((zcode) == (code) && (ldz) % 8 == 0))
-#define LAUNCH_T(dtype, KERN, grid, ...)                                                               \
-    do {                                                                                               \
-        if ((dtype) == TEDSPAD_F16) hipLaunchKernelGGL(KERN<F16>, grid, dim3(256), 0, s, __VA_ARGS__); \
-        else hipLaunchKernelGGL(KERN<BF16>, grid, dim3(256), 0, s, __VA_ARGS__);                       \
-    } while (0)
 
 namespace tedspad {
 namespace {
@@ -717,7 +706,7 @@ extern "C" int32_t tedspad_scale_shift_act(const float *z, const float *scale, c
                                            int32_t C, int32_t ldz, int32_t ldres, int32_t ldy, int32_t relu, int32_t dtype, void *stream) {
     TS_REQUIRE(z && scale && shift && y && pixels > 0 && C > 0 && C % 8 == 0 && ldz % 4 == 0 && ldy % 8 == 0 && TS_DT(dtype) && (uintptr_t)z % 16 == 0, "tedspad_scale_shift_act: bad arguments");
     hipStream_t s = (hipStream_t)stream;
-    LAUNCH_T(dtype, bn_apply_kernel, dim3(grid_for(pixels * (C / 8))), z, scale, shift, (const uint16_t *)res, (uint16_t *)y, (long)pixels, C / 8, ldz, ldres, ldy, relu);
+    TS_LAUNCH_T(dtype, bn_apply_kernel<T>, dim3(grid_for(pixels * (C / 8))), dim3(256), 0, s, z, scale, shift, (const uint16_t *)res, (uint16_t *)y, (long)pixels, C / 8, ldz, ldres, ldy, relu);
     return check_launch("tedspad_scale_shift_act");
 }
 
@@ -741,8 +730,7 @@ extern "C" int32_t tedspad_bn_bwd_reduce(const void *dy, const void *y, const vo
     const bool unroll = uf_env ? uf_env > 1 : pixels / (pblocks * PL) < 48;
 #define BNR_ARGS dim3((unsigned)(pblocks * cgroups), groups), dim3(256), 0, s, (const uint16_t *)dy, (const uint16_t *)y, z, (int)(zdtype != TEDSPAD_F32), mean, invstd, gamma, beta, \
                  sums, sums_ld, (long)pixels, C8, lddy, ldy, ldz, relu
-    if (dtype == TEDSPAD_F16) { if (unroll) hipLaunchKernelGGL((bn_bwd_reduce_kernel<F16, 4>), BNR_ARGS); else hipLaunchKernelGGL((bn_bwd_reduce_kernel<F16, 1>), BNR_ARGS); }
-    else { if (unroll) hipLaunchKernelGGL((bn_bwd_reduce_kernel<BF16, 4>), BNR_ARGS); else hipLaunchKernelGGL((bn_bwd_reduce_kernel<BF16, 1>), BNR_ARGS); }
+    TS_WITH_T(dtype, if (unroll) hipLaunchKernelGGL((bn_bwd_reduce_kernel<T, 4>), BNR_ARGS); else hipLaunchKernelGGL((bn_bwd_reduce_kernel<T, 1>), BNR_ARGS));
 #undef BNR_ARGS
     return check_launch("tedspad_bn_bwd_reduce");
 }
@@ -754,12 +742,11 @@ extern "C" int32_t tedspad_bn_bwd_apply(const void *dy, const void *y, const voi
                "tedspad_bn_bwd_apply: bad arguments (relu needs y, or beta to recompute the mask)");
     hipStream_t s = (hipStream_t)stream;
     // (the grid below decides which `dbias` rows a launch can touch: tests/test_hip_train_kernels.py apply_grid restates grid_for_iters(items, 8) -- change both together)
-#define BWD_APPLY(TT, DD)                                                                                                                            \
-    hipLaunchKernelGGL((bn_bwd_apply_kernel<TT, DD>), dim3(grid_for_iters(pixels * (C / 8), 8), groups), dim3(256), (size_t)C * 16, s, (const uint16_t *)dy, (const uint16_t *)y, z, \
+#define BWD_APPLY(DD)                                                                                                                                \
+    hipLaunchKernelGGL((bn_bwd_apply_kernel<T, DD>), dim3(grid_for_iters(pixels * (C / 8), 8), groups), dim3(256), (size_t)C * 16, s, (const uint16_t *)dy, (const uint16_t *)y, z, \
                        (int)(zdtype != TEDSPAD_F32), mean, invstd, gamma, beta, sums, sums_ld, 1.f / (float)pixels, (uint16_t *)dz, (uint16_t *)dres, dbias,      \
                        dbias_slots, (long)pixels, C / 8, lddy, ldy, ldz, lddz, lddres, relu)
-    if (dtype == TEDSPAD_F16) { if (dbias) BWD_APPLY(F16, true); else BWD_APPLY(F16, false); }
-    else { if (dbias) BWD_APPLY(BF16, true); else BWD_APPLY(BF16, false); }
+    TS_WITH_T(dtype, if (dbias) BWD_APPLY(true); else BWD_APPLY(false));
 #undef BWD_APPLY
     return check_launch("tedspad_bn_bwd_apply");
 }
@@ -777,14 +764,11 @@ extern "C" int32_t tedspad_maxpool_bwd(const tedspad_pool_desc *d, const void *x
     hipStream_t s = (hipStream_t)stream;
     if (p.total < (1L << 31) && d->kt == 1 && d->kh == 2 && d->kw == 2 && d->st == 1 && d->sh == 2 && d->sw == 2 && d->pt == 0 && d->ph == 0 && d->pw == 0 &&
         d->h % 2 == 0 && d->w % 2 == 0 && d->to == d->t && d->ho == d->h / 2 && d->wo == d->w / 2) {
-        LAUNCH_T(d->dtype, maxpool_bwd_k2s2_kernel, dim3(grid_for(p.total)), p);
+        TS_LAUNCH_T(d->dtype, maxpool_bwd_k2s2_kernel<T>, dim3(grid_for(p.total)), dim3(256), 0, s, p);
         return check_launch("tedspad_maxpool_bwd");
     }
-    if (p.total < (1L << 31)) {
-        if (d->dtype == TEDSPAD_F16) hipLaunchKernelGGL((maxpool_bwd_kernel<F16, unsigned>), dim3(grid_for(p.total)), dim3(256), 0, s, p);
-        else hipLaunchKernelGGL((maxpool_bwd_kernel<BF16, unsigned>), dim3(grid_for(p.total)), dim3(256), 0, s, p);
-    } else
-    LAUNCH_T(d->dtype, maxpool_bwd_kernel, dim3(grid_for(p.total)), p);
+    if (p.total < (1L << 31)) TS_LAUNCH_T(d->dtype, (maxpool_bwd_kernel<T, unsigned>), dim3(grid_for(p.total)), dim3(256), 0, s, p);
+    else TS_LAUNCH_T(d->dtype, maxpool_bwd_kernel<T>, dim3(grid_for(p.total)), dim3(256), 0, s, p);
     return check_launch("tedspad_maxpool_bwd");
 }
 
@@ -792,7 +776,7 @@ extern "C" int32_t tedspad_global_avgpool_bwd(const float *dfeat, const void *ma
                                               int32_t lddx, int32_t dtype, void *stream) {
     TS_REQUIRE(dfeat && dx && n > 0 && spatial > 0 && c % 8 == 0 && lddx >= c && TS_DT(dtype), "tedspad_global_avgpool_bwd: bad arguments");
     hipStream_t s = (hipStream_t)stream;
-    LAUNCH_T(dtype, avgpool_bwd_kernel, dim3(grid_for((long)n * spatial * (c / 8))), dfeat, (const uint16_t *)mask, ldmask, (uint16_t *)dx, n, spatial, c / 8, lddx);
+    TS_LAUNCH_T(dtype, avgpool_bwd_kernel<T>, dim3(grid_for((long)n * spatial * (c / 8))), dim3(256), 0, s, dfeat, (const uint16_t *)mask, ldmask, (uint16_t *)dx, n, spatial, c / 8, lddx);
     return check_launch("tedspad_global_avgpool_bwd");
 }
 
@@ -803,11 +787,8 @@ extern "C" int32_t tedspad_upsample_bilinear2x_bwd(const void *dy, void *dx, int
                "tedspad_upsample_bilinear2x_bwd: bad arguments");
     const long total = (long)n * h * w * (c / 8);
     hipStream_t s = (hipStream_t)stream;
-    if (total < (1L << 31)) {
-        if (dtype == TEDSPAD_F16) hipLaunchKernelGGL((upsample2x_bwd_kernel<F16, unsigned>), dim3(grid_for(total)), dim3(256), 0, s, (const uint16_t *)dy, (uint16_t *)dx, h, w, c / 8, lddy, lddx, ho, wo, pad_top, pad_left, total);
-        else hipLaunchKernelGGL((upsample2x_bwd_kernel<BF16, unsigned>), dim3(grid_for(total)), dim3(256), 0, s, (const uint16_t *)dy, (uint16_t *)dx, h, w, c / 8, lddy, lddx, ho, wo, pad_top, pad_left, total);
-    } else
-    LAUNCH_T(dtype, upsample2x_bwd_kernel, dim3(grid_for(total)), (const uint16_t *)dy, (uint16_t *)dx, h, w, c / 8, lddy, lddx, ho, wo, pad_top, pad_left, total);
+    if (total < (1L << 31)) TS_LAUNCH_T(dtype, (upsample2x_bwd_kernel<T, unsigned>), dim3(grid_for(total)), dim3(256), 0, s, (const uint16_t *)dy, (uint16_t *)dx, h, w, c / 8, lddy, lddx, ho, wo, pad_top, pad_left, total);
+    else TS_LAUNCH_T(dtype, upsample2x_bwd_kernel<T>, dim3(grid_for(total)), dim3(256), 0, s, (const uint16_t *)dy, (uint16_t *)dx, h, w, c / 8, lddy, lddx, ho, wo, pad_top, pad_left, total);
     return check_launch("tedspad_upsample_bilinear2x_bwd");
 }
 
@@ -816,7 +797,7 @@ extern "C" int32_t tedspad_nchw_grad_to_channels_last(const float *dy, const flo
     TS_REQUIRE(dy && out && n > 0 && c > 0 && c <= 8 && thw > 0 && TS_DT(dtype), "tedspad_nchw_grad_to_channels_last: bad arguments");
     const long total = (long)n * thw;
     hipStream_t s = (hipStream_t)stream;
-    LAUNCH_T(dtype, nchw_grad_to_cl_kernel, dim3(grid_for(total)), dy, y_sigmoid, (uint16_t *)out, c, (long)thw, total);
+    TS_LAUNCH_T(dtype, nchw_grad_to_cl_kernel<T>, dim3(grid_for(total)), dim3(256), 0, s, dy, y_sigmoid, (uint16_t *)out, c, (long)thw, total);
     return check_launch("tedspad_nchw_grad_to_channels_last");
 }
 
@@ -825,7 +806,7 @@ extern "C" int32_t tedspad_channels_last_to_nchw_strided(const void *x, float *y
     TS_REQUIRE(x && y && n > 0 && c > 0 && ldx >= c && TS_DT(dtype), "tedspad_channels_last_to_nchw_strided: bad arguments");
     const long total = (long)n * t * h * w;
     hipStream_t s = (hipStream_t)stream;
-    LAUNCH_T(dtype, cl_to_nchw_strided_kernel, dim3(grid_for(total)), (const uint16_t *)x, y, c, t, h, w, ldx, (long)sn, (long)sc, (long)st_, (long)sh, (long)sw, total);
+    TS_LAUNCH_T(dtype, cl_to_nchw_strided_kernel<T>, dim3(grid_for(total)), dim3(256), 0, s, (const uint16_t *)x, y, c, t, h, w, ldx, (long)sn, (long)sc, (long)st_, (long)sh, (long)sw, total);
     return check_launch("tedspad_channels_last_to_nchw_strided");
 }
 
@@ -844,8 +825,7 @@ extern "C" int32_t tedspad_bn_train_apply(const void *z, int32_t zdtype, const f
     const bool unroll = uf_env ? uf_env > 1 : (Cz >= 256 && pixels * (Cz / 8) / ((long)gx * 256) <= 16);
 #define BNA_ARGS dim3(gx, groups), dim3(256), 0, s, z, (int)(zdtype != TEDSPAD_F32), stats, stats_ld, (float)count, gamma, beta, eps, momentum, running_mean, running_var, mean, invstd, C, \
                  (const uint16_t *)res, (uint16_t *)y, (long)pixels, Cz / 8, ldz, ldres, ldy, relu
-    if (dtype == TEDSPAD_F16) { if (unroll) hipLaunchKernelGGL((bn_train_apply_kernel<F16, 4>), BNA_ARGS); else hipLaunchKernelGGL((bn_train_apply_kernel<F16, 1>), BNA_ARGS); }
-    else { if (unroll) hipLaunchKernelGGL((bn_train_apply_kernel<BF16, 4>), BNA_ARGS); else hipLaunchKernelGGL((bn_train_apply_kernel<BF16, 1>), BNA_ARGS); }
+    TS_WITH_T(dtype, if (unroll) hipLaunchKernelGGL((bn_train_apply_kernel<T, 4>), BNA_ARGS); else hipLaunchKernelGGL((bn_train_apply_kernel<T, 1>), BNA_ARGS));
 #undef BNA_ARGS
     return check_launch("tedspad_bn_train_apply");
 }
