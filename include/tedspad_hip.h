@@ -541,6 +541,43 @@ int32_t tedspad_frames_crop_resize_pil(const void *frames, int32_t T, int32_t H,
                                        int32_t cw, int32_t oh, int32_t ow, const int32_t *ytab, int32_t ytaps, const int32_t *xtab,
                                        int32_t xtaps, float *out, int64_t so_t, int64_t so_c, int64_t so_h, int64_t so_w, void *stream);
 
+/* The training loaders' per-frame augmentation (aux_code/ucf101_dl.py: contrastive_train_dataloader.augmentation :596-630 / weak_augmentation :632-642,
+ * single_train_dataloader.augmentation :149-183) for a whole batch in ONE launch: uint8 (H,W,3) frame -> resized_crop (Pillow crop, zero-filled right of and
+ * below the frame, + two-pass BILINEAR resize, as tedspad_frames_crop_resize_pil) -> contrast / hue / saturation / brightness / contrast / grayscale + gamma
+ * (Pillow's 8-bit ImageEnhance / HSV / point arithmetic) -> hflip -> to_tensor (/255) -> two erased boxes -> fp32
+ * out[dst + c*so_c + y*so_h + x*so_w]. One record per OUTPUT frame, so frames of different videos (sizes), per-clip and per-frame parameters share the launch.
+ * `blob_host`: HOST bytes {nrec records | int32 Pillow tables | 256-byte gamma tables}, copied to `blob_dev` (blob_bytes device bytes, 8-byte aligned) on
+ * `stream` before the launch (the one upload); the records' table offsets are int32-word offsets from tables_off, rows of (2 + taps) words
+ * {first index, count, 22-bit coefficients} (ted_spad_amd/preprocess.pil_table) for crop height -> oh and crop width -> ow. Every record, every table
+ * row it names and the extent of its output frame inside out_elems are checked on the host before anything is launched. One workgroup per record holds
+ * the resized frame in LDS: 3*oh*ow bytes must fit (TEDSPAD_EUNSUPPORTED above 224 x 224). Bit-exact with Pillow (tests/test_hip_augment.py). */
+enum {
+    TEDSPAD_AUG_CONTRAST_FIRST = 1,     /* adjust_contrast before hue (:606) */
+    TEDSPAD_AUG_HUE = 2,
+    TEDSPAD_AUG_SATURATION = 4,
+    TEDSPAD_AUG_BRIGHTNESS = 8,
+    TEDSPAD_AUG_CONTRAST_LATE = 16,     /* adjust_contrast after brightness (:614) */
+    TEDSPAD_AUG_GRAY = 32,
+    TEDSPAD_AUG_GAMMA = 64,             /* only together with TEDSPAD_AUG_GRAY (:616-619) */
+    TEDSPAD_AUG_HFLIP = 128,
+    TEDSPAD_AUG_REVERSE = 256           /* read the source channels in reverse order (single_train_dataloader :124) */
+};
+typedef struct tedspad_augment_record {
+    const uint8_t *src;                 /* the (H, W, 3) uint8 source frame */
+    int64_t dst;                        /* element offset of the output frame in `out` */
+    int32_t H, W;
+    int32_t top, left, ch, cw;          /* crop box; top + ch > H and left + cw > W are allowed (zero fill), negative origins are not */
+    int32_t ytab, xtab, ytaps, xtaps;   /* the two tables: word offsets and taps per row */
+    int32_t flags;                      /* TEDSPAD_AUG_* */
+    int32_t gamma_lut;                  /* index of the 256-byte table adjust_gamma's point() uses */
+    float contrast, saturation, brightness;     /* Image.blend factors */
+    int32_t hue_off;                    /* uint8(hue_factor * 255), 0..255: added to H modulo 256 */
+    int32_t erase[8];                   /* two boxes {i (row), j (column), h, w}; h <= 0 or w <= 0: none. Clipped at the borders like a slice */
+} tedspad_augment_record;
+int32_t tedspad_clip_augment(const void *blob_host, void *blob_dev, int64_t blob_bytes, int32_t nrec, int64_t tables_off, int64_t table_words,
+                             int64_t luts_off, int32_t nluts, float *out, int64_t out_elems, int32_t oh, int32_t ow, int64_t so_c, int64_t so_h,
+                             int64_t so_w, void *stream);
+
 /* MGFN feature feed (anomaly_detection_mgfn/datasets/dataset.py:65-100): feat (T, ncrops, F) fp32.
  * length > 0 (train): out (ncrops, length, F+1) = process_feat (utils/utils.py:34-42: means over the
  * numpy.linspace(0,T,length+1,dtype=int) segments, a single row where a segment is empty) + L2 magnitude channel.
