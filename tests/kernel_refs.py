@@ -1,5 +1,6 @@
 """float64 references of the memory-bound training kernels (csrc/train_ops.hip, the idx / backward half of csrc/pool_layout.hip, csrc/head.hip, csrc/loss.hip)
-and the two value generators their tests use; at the end, the exact-arithmetic conv references and case tables of tests/test_hip_conv_exact.py. A plain helper module: tests/test_kernel_refs.py checks every reference here against float64 torch (autograd) on
+and the two value generators their tests use; then the exact-arithmetic conv references and case tables of tests/test_hip_conv_exact.py and, at the end, the chain
+references, input conditions and case tables of the fused forward kernels (tests/test_hip_fused_exact.py). A plain helper module: tests/test_kernel_refs.py checks every reference here against float64 torch (autograd) on
 the CPU, the -m gpu op tests (test_hip_train_kernels.py, test_hip_head_ops.py, test_hip_losses.py) compare the kernels with them.
 
 Activations are channels-last: (pixels, C) for the BatchNorm kernels, (n, t, h, w, c) for the pools, (n, h, w, c) for the resizes. Everything returned is a
@@ -517,3 +518,353 @@ def signed_zero_mask(seed, name, shape):
     """Mask values drawn from {-1, -0.0, +0.0, 1}: only the last keeps the element (mask > 0)."""
     u = synth_tensor(seed, name, shape).to(D)
     return torch.tensor([-1.0, -0.0, 0.0, 1.0, 1.0, 1.0], dtype=D)[torch.floor(6.0 * u).long().clamp_(0, 5)]
+
+
+# ---- exact-arithmetic references of the fused forward kernels (tests/test_hip_fused_exact.py) -------------------------------------------------------------
+# The same method carried through the fused stages: integer inputs, integer weights, power-of-two BatchNorm scales and integer shifts keep every value of
+# a stage on a dyadic grid (its `step`: the input's step times the smallest scale) and every fp32 partial sum exact; the ONE rounding of a 16-bit
+# intermediate is round-to-nearest-even of an exactly known number (round_once), and a rounded grid value is still on the grid, so the next stage is exact
+# again. A fused kernel must equal these references bit for bit. A stage is (w, stride, (pads_front, pads_back), scale, shift, residual, relu).
+def same(got, want, what, fails=None, detail=None):
+    """torch.equal, with the count and the first differing index on a mismatch (+ detail(got, want), a test's own words about where). With `fails`, a list, the
+    message is appended to it instead of raised."""
+    msg = first_mismatch(got, want)
+    if msg and detail is not None:
+        msg += detail(got, want)
+    if not msg and not torch.equal(got, want):           # a NaN on both sides: first_mismatch lets it pass, torch.equal does not
+        msg = "not torch.equal"
+    if msg:
+        print("%s: %s" % (what, msg))
+    if fails is not None:
+        if msg:
+            fails.append("%s: %s" % (what, msg))
+        return not msg
+    assert not msg, "%s: %s" % (what, msg)
+    return True
+
+
+def pow2_scales(c, exps=(-1, -2)):
+    """Per-channel scales 2^exps[c % len(exps)]: neighbouring channels differ."""
+    return torch.tensor([2.0 ** e for e in exps], dtype=D)[torch.arange(c) % len(exps)]
+
+
+def nonzero_ints(seed, name, shape, lo=-8, hi=8):
+    """Integers in [lo, hi] without 0 (a 0 becomes 3)."""
+    v = small_ints(seed, name, shape, lo=lo, hi=hi, density=1.0)
+    return torch.where(v == 0, torch.full_like(v, 3.0), v)
+
+
+def exact_in_fp32_steps(abs_sum, step):
+    """The exactness gate on a dyadic grid: `abs_sum` (a compared quantity recomputed on absolute values) in units of the power-of-two `step` is an integer
+    below 2^24, so every partial sum the kernel can form, in any order, is a multiple of `step` that fp32 holds exactly."""
+    assert step > 0 and float(np.log2(step)) == round(float(np.log2(step))), step
+    return exact_in_fp32(torch.as_tensor(abs_sum).to(D) / step)
+
+
+def chain_ref64(x, stages, dtype, step=1.0, fp32_out=False):
+    """x (n, c, t, h, w) on a grid of `step` through the stages; every stage's output is rounded once to `dtype` (the last one not with fp32_out: a kernel
+    that stores fp32). Returns one dict per stage: y (rounded, float64), raw (before the rounding, after the ReLU), abs (sum |x||w| scale + |shift| +
+    |residual| on the rounded input), step (the grid of raw)."""
+    out, cur = [], x.to(D)
+    for i, (w, stride, (pf, pb), scale, shift, residual, relu) in enumerate(stages):
+        raw, _ = conv_fwd_ref64(cur, w, stride, pf, pb, scale=scale, shift=shift, residual=residual, relu=relu)
+        _, a = conv_fwd_ref64(cur.abs(), w.abs(), stride, pf, pb, scale=scale, shift=None if shift is None else torch.as_tensor(shift).abs())
+        if residual is not None:
+            a = a + residual.to(D).abs()
+        if scale is not None:
+            step = step * float(torch.as_tensor(scale).abs().min())
+        last = i == len(stages) - 1
+        y = raw.clone() if (last and fp32_out) else round_once(raw, dtype)
+        out.append({"y": y, "raw": raw, "abs": a, "step": step, "stored16": not (last and fp32_out), "relu": relu})
+        cur = y
+    return out
+
+
+def rounding_stats(raw, dtype):
+    """(share of elements the 16-bit store changes, number of exact ties among them that round-to-nearest-even resolves TOWARDS zero: rounding half away from
+    zero gets those wrong). v is a tie iff its mirror image 2 v - r about the rounded value r is representable too."""
+    r = round_once(raw, dtype)
+    moved = r != raw
+    mirror = 2.0 * raw - r
+    tie = moved & (mirror.to(torch.float32).to(TDT[dtype]).to(D) == mirror)
+    return float(moved.double().mean()), int((tie & (r.abs() < raw.abs())).sum())
+
+
+def fused_conditions(stages, dtype, what="", mix=None):
+    """Conditions 1-3 on a chain_ref64 result (or any list of such dicts), asserted; returns per 16-bit stage (rounded share, ties towards zero) and prints
+    the largest absolute-value sum in steps. 1: every absolute-value sum in units of the stage's step is an integer below 2^24. 2: every stored 16-bit value is
+    below 65504 in magnitude (the inference store saturates, the reference does not). 3: every stage with a ReLU is alive: >= 25 % positive, >= 25 % zero.
+    4, with a `mix` that promises it for this type (Mix.rounds): the store of every 16-bit stage before the last changes >= 1 % of it, exact ties among them."""
+    stats = []
+    for i, s in enumerate(stages):
+        assert exact_in_fp32_steps(s["abs"], s["step"])
+        if s["stored16"]:
+            assert float(s["y"].abs().max()) < 65504.0, (what, i, float(s["y"].abs().max()))
+        pos, zero = float((s["y"] > 0).double().mean()), float((s["y"] == 0).double().mean())
+        if s["relu"]:
+            assert pos >= 0.25 and zero >= 0.25, (what, i, pos, zero)
+        st = rounding_stats(s["raw"], dtype) if s["stored16"] else (0.0, 0)
+        stats.append(st)
+        print("%s %s stage %d: largest |sum| %.0f steps of 2^%d, largest value %.1f, positive %.2f, zero %.2f, rounded %.3f, ties to even towards zero %d" % (
+            what, dtype, i, float(s["abs"].max()) / s["step"], round(float(np.log2(s["step"]))), float(s["y"].abs().max()), pos, zero, st[0], st[1]))
+        if mix is not None and dtype in mix.rounds and i < len(stages) - 1:
+            assert rounding_happens(stats, i), (what, dtype, i, st)
+    return stats
+
+
+def rounding_happens(stats, stage):
+    """Condition 4 for one (case, dtype): at least 1 % of the intermediate `stage` is changed by its store, exact ties among them."""
+    return stats[stage][0] >= 0.01 and stats[stage][1] >= 1
+
+
+def bn_is_telling(scale, shift):
+    """Condition 5: the scales are powers of two that differ between neighbouring channels, the shifts non-zero integers (a swapped or shifted channel index
+    changes the result). `scale` None: a plain bias."""
+    shift = torch.as_tensor(shift).to(D)
+    assert bool((shift != 0).all()) and bool((shift == shift.round()).all())
+    if scale is not None:
+        e = torch.log2(torch.as_tensor(scale).to(D))
+        assert bool((e == e.round()).all()) and bool((e[1:] != e[:-1]).all())
+    return True
+
+
+def dual_ref64(x, w1, s1, b1, x2, w2, s2, b2, stride2=1, relu=True):
+    """relu(s1 * conv(x, w1) + b1 + s2 * conv_strided(x2, w2) + b2) for two 1x1x1 convs, the second sampling x2 with the spatial stride `stride2` on the first
+    one's pixels. Returns (raw, abs): abs on absolute values."""
+    z, st = (0, 0, 0), (1, stride2, stride2)
+    h, w = x.shape[3], x.shape[4]
+    def two(xa, wa, xb, wb, ba, bb):
+        _, a = conv_fwd_ref64(xa, wa, (1, 1, 1), z, z, scale=s1, shift=ba)
+        _, b = conv_fwd_ref64(xb, wb, st, z, z, scale=s2, shift=bb)
+        return a + b[:, :, :, :h, :w]
+    raw = two(x, w1, x2, w2, b1, b2)
+    return (raw.clamp_min(0.0) if relu else raw), two(x.abs(), w1.abs(), x2.abs(), w2.abs(), b1.abs(), b2.abs())
+
+
+def pair_max_t(y):
+    """max over frame pairs (2 k, 2 k + 1) of (n, c, t, h, w); an unpaired last frame is dropped as nn.MaxPool3d((2, 1, 1), (2, 1, 1)) does."""
+    tp = y.shape[2] // 2
+    return torch.maximum(y[:, :, 0:2 * tp:2], y[:, :, 1:2 * tp:2])
+
+
+def max_pool_ref64(y, k, s):
+    return F.max_pool3d(y.to(D), tuple(k), tuple(s))
+
+
+def upsample2x_nchw(x):
+    """nearest x2 along h and w of (n, c, t, h, w)."""
+    return x.repeat_interleave(2, dim=3).repeat_interleave(2, dim=4)
+
+
+P0, P011 = ((0, 0, 0), (0, 0, 0)), ((0, 1, 1), (0, 1, 1))
+ONE = (1, 1, 1)
+
+
+class Mix:
+    """How a fused case draws its integers: activations in [-x_hi, x_hi] at x_density, per conv the weights in [-hi, hi] at a density, the scale exponents."""
+
+    def __init__(self, x_hi, x_density, weights, exps=(-1, -2), rounds=()):
+        """rounds: the types whose 16-bit intermediates the mix promises to round, ties included (condition 4; fused_conditions asserts it)."""
+        self.x_hi, self.x_density, self.weights, self.exps, self.rounds = x_hi, x_density, weights, exps, tuple(rounds)
+
+    def x(self, seed, name, shape):
+        return small_ints(seed, name, shape, lo=-self.x_hi, hi=self.x_hi, density=self.x_density)
+
+    def w(self, i, seed, name, shape):
+        hi, density = self.weights[i]
+        return small_ints(seed, name, shape, lo=-hi, hi=hi, density=density)
+
+    def bn(self, seed, name, c):
+        return pow2_scales(c, self.exps), nonzero_ints(seed, name + "b", (c,))
+
+
+BOTH = ("f16", "bf16")
+SMALL = Mix(2, 0.5, [(2, 0.1), (2, 0.1), (2, 0.25)])              # bf16 rounds the second intermediate only, f16 neither
+BIG = Mix(8, 1.0, [(16, 1.0), (2, 0.03), (2, 0.03)], rounds=BOTH)              # stage sums above 2048 steps: f16 rounds too
+
+
+class BneckFrameCase:
+    """engine.BneckFrame: conv1 (1x1x1 | 3x1x1, 1024 -> 256) -> conv2 (1x3x3) -> conv3 (256 -> 1024) + the input as residual, 14 x 14 frames."""
+
+    def __init__(self, name, temporal, n, t, mix):
+        self.name, self.temporal, self.n, self.t, self.mix = name, temporal, n, t, mix
+
+    def tensors(self, seed=23):
+        m, nm, kt = self.mix, self.name, 3 if self.temporal else 1
+        x = m.x(seed, nm + "x", (self.n, 1024, self.t, 14, 14))
+        ws = [m.w(0, seed, nm + "w1", (256, 1024, kt, 1, 1)), m.w(1, seed, nm + "w2", (256, 256, 1, 3, 3)), m.w(2, seed, nm + "w3", (1024, 256, 1, 1, 1))]
+        bn = [m.bn(seed, nm + "bn%d" % i, c) for i, c in enumerate((256, 256, 1024))]
+        return x, ws, bn
+
+    def stages(self, x, ws, bn):
+        pt = ((1, 0, 0), (1, 0, 0)) if self.temporal else P0
+        return [(ws[0], ONE, pt, bn[0][0], bn[0][1], None, True), (ws[1], ONE, P011, bn[1][0], bn[1][1], None, True), (ws[2], ONE, P0, bn[2][0], bn[2][1], x, True)]
+
+
+BNECK_FRAME_CASES = [BneckFrameCase("plain_1x3", False, 1, 3, SMALL), BneckFrameCase("plain_3x2_big", False, 3, 2, BIG),
+                     BneckFrameCase("temporal_2x2", True, 2, 2, SMALL), BneckFrameCase("temporal_1x2_big", True, 1, 2, BIG)]
+
+
+TAIL_SMALL = Mix(8, 1.0, [(4, 1.0), (2, 0.25), (2, 0.25)], rounds=("bf16",))       # the 64 / 128-channel intermediate above 256 steps: bf16 rounds it
+TAIL_BIG = Mix(8, 1.0, [(32, 1.0), (2, 0.25), (2, 0.25)], rounds=BOTH)        # ... above 2048 steps: f16 rounds it too
+
+
+class BneckTailCase:
+    """engine.BneckTail: conv2 (1x3x3, cmid -> cmid) -> conv3 (cmid -> 4 cmid) + residual | + the downsample branch on x2 (64 -> 256) | + residual and the
+    temporal pair max. `forms`: which of 'residual', 'dual', 'pool' the case runs (the 128-channel kernel is the plain block only; the pool needs an even t)."""
+
+    def __init__(self, dims, cmid, mix):
+        self.dims, self.cmid, self.cout3, self.mix = tuple(dims), cmid, 4 * cmid, mix
+        self.name = "c%d_%dx%dx%dx%d" % ((cmid,) + self.dims)
+        self.forms = ("residual",) if cmid == 128 else ("residual", "dual") + (("pool",) if dims[1] % 2 == 0 else ())
+
+    def tensors(self, seed=29):
+        m, nm, c, (n, t, h, w) = self.mix, self.name, self.cmid, self.dims
+        d = {"x": m.x(seed, nm + "x", (n, c, t, h, w)), "w2": m.w(0, seed, nm + "w2", (c, c, 1, 3, 3)), "w3": m.w(1, seed, nm + "w3", (self.cout3, c, 1, 1, 1)),
+             "res": nonzero_ints(seed, nm + "r", (n, self.cout3, t, h, w))}
+        d["s2"], d["b2"] = m.bn(seed, nm + "bn2", c)
+        d["s3"], d["b3"] = m.bn(seed, nm + "bn3", self.cout3)
+        if c == 64:
+            d["x2"], d["wd"] = m.x(seed, nm + "x2", (n, 64, t, h, w)), m.w(2, seed, nm + "wd", (self.cout3, 64, 1, 1, 1))
+            d["sd"], d["bd"] = pow2_scales(self.cout3, tuple(reversed(m.exps))), nonzero_ints(seed, nm + "bnd", (self.cout3,))
+        return d
+
+    def reference(self, d, dtype):
+        """{form: [mid stage, output stage]} as chain_ref64 gives them; 'dual' adds the second conv to the output stage, 'pool' takes the pair max of 'residual'."""
+        mid = chain_ref64(d["x"], [(d["w2"], ONE, P011, d["s2"], d["b2"], None, True)], dtype)[0]
+        out = {}
+        for form in self.forms:
+            if form == "dual":
+                raw, a = dual_ref64(mid["y"], d["w3"], d["s3"], d["b3"], d["x2"], d["wd"], d["sd"], d["bd"])
+                step = mid["step"] * 0.25
+                out[form] = [mid, {"y": round_once(raw, dtype), "raw": raw, "abs": a, "step": step, "stored16": True, "relu": True}]
+            else:
+                last = chain_ref64(mid["y"], [(d["w3"], ONE, P0, d["s3"], d["b3"], d["res"], True)], dtype, step=mid["step"])[0]
+                if form == "pool":
+                    last = dict(last, y=pair_max_t(last["y"]), raw=pair_max_t(last["raw"]))
+                out[form] = [mid, last]
+        return out
+
+
+BNECK_TAIL64_CASES = [BneckTailCase((2, 3, 7, 9), 64, TAIL_BIG), BneckTailCase((1, 1, 16, 16), 64, TAIL_SMALL), BneckTailCase((3, 6, 9, 11), 64, TAIL_SMALL),
+                      BneckTailCase((1, 2, 20, 55), 64, TAIL_BIG)]
+BNECK_TAIL128_CASES = [BneckTailCase((2, 3, 7, 9), 128, TAIL_BIG), BneckTailCase((1, 1, 16, 16), 128, TAIL_SMALL), BneckTailCase((4, 2, 14, 30), 128, TAIL_SMALL)]
+
+UPP_SMALL = Mix(8, 1.0, [(4, 1.0), (2, 0.1), (2, 0.1)], rounds=("bf16",))
+UPP_BIG = Mix(8, 1.0, [(32, 1.0), (2, 0.1), (2, 0.1)], rounds=BOTH)
+
+
+class UppTailCase:
+    """tedspad_unetpp_tail_fwd: nearest x2 of the (n, h / 2, w / 2, 64) input -> conv-bn-relu 64 -> 32 -> conv-bn-relu 32 -> 32 -> the 3x3 head 32 -> 3 + bias, fp32
+    (n, 3, h, w). `walk`: more than twice as many 16 x 16 patches as the device has compute units (256; the grid is min(patches, units)), so workgroups walk two and three
+    patches: the head of a patch runs inside the loop, and the third patch is fetched into an X buffer that the first one used."""
+
+    def __init__(self, n, h, w, mix, walk=False):
+        self.n, self.h, self.w, self.mix, self.walk = n, h, w, mix, walk
+        self.name = "%dx%dx%d" % (n, h, w)
+        self.npatch = n * ((h + 15) // 16) * ((w + 15) // 16)
+
+    def tensors(self, seed=31):
+        m, nm = self.mix, self.name
+        d = {"x": m.x(seed, nm + "x", (self.n, 64, 1, self.h // 2, self.w // 2)), "w1": m.w(0, seed, nm + "w1", (32, 64, 1, 3, 3)),
+             "w2": m.w(1, seed, nm + "w2", (32, 32, 1, 3, 3)), "w3": m.w(2, seed, nm + "w3", (3, 32, 1, 3, 3)), "bias": nonzero_ints(seed, nm + "b3", (3,))}
+        d["s1"], d["b1"] = m.bn(seed, nm + "bn1", 32)
+        d["s2"], d["b2"] = m.bn(seed, nm + "bn2", 32)
+        return d
+
+    def reference(self, d, dtype):
+        return chain_ref64(upsample2x_nchw(d["x"]), [(d["w1"], ONE, P011, d["s1"], d["b1"], None, True), (d["w2"], ONE, P011, d["s2"], d["b2"], None, True),
+                                                     (d["w3"], ONE, P011, None, d["bias"], None, False)], dtype, fp32_out=True)
+
+
+UPP_TAIL_CASES = [UppTailCase(1, 16, 16, UPP_BIG), UppTailCase(2, 18, 34, UPP_SMALL), UppTailCase(3, 48, 80, UPP_BIG), UppTailCase(2, 2, 2, UPP_SMALL),
+                  UppTailCase(6, 138, 170, UPP_SMALL, walk=True)]
+
+
+# ---- the single-stage fused kernels: no 16-bit intermediate, one store --------------------------------------------------------------------------------------
+POINT = Mix(8, 1.0, [(4, 1.0), (4, 1.0)])
+STEM = Mix(4, 1.0, [(2, 1.0)])
+TPAIR_CASES = [(1, 5, 3, 128, 256), (3, 9, 11, 512, 384)]                                     # n, h, w, cin, cout
+DUAL_CASES = [((3, 4, 11, 13), 256, 64), ((1, 2, 30, 31), 256, 128), ((2, 1, 5, 5), 64, 64)]        # dims, cout, ld2
+DUAL_P8_CASES = [((3, 2, 14, 14), 128, 256, 512, 2), ((2, 2, 7, 9), 256, 512, 1024, 2), ((1, 3, 5, 5), 64, 64, 256, 1), ((2, 1, 28, 27), 128, 64, 256, 2)]
+POOL_T2_CASES = [((2, 5, 7, 9), 128, 72, False), ((2, 2, 16, 16), 64, 64, True)]                # dims, cin, cout, residual
+STEM_CASES = [(2, 3, 16, 32, 32), (3, 3, 5, 18, 72), (1, 2, 8, 66, 24)]                         # n, c, t, h, w
+
+
+def _stage(raw, a, step, dtype, relu=True):
+    return {"y": round_once(raw, dtype), "raw": raw, "abs": a, "step": step, "stored16": True, "relu": relu}
+
+
+def negative_ints(seed, name, shape, lo=-8):
+    """Integers in [lo, -1]: a stage whose output is a max over several ReLU outputs keeps a quarter of zeros only if most of them are zero."""
+    return -nonzero_ints(seed, name, shape, lo=lo, hi=-lo).abs()
+
+
+def tpair_reference(case, dtype, seed=37):
+    """engine.TPairConv: a 3x1x1 'same' conv + BN + ReLU on a two-frame tensor."""
+    n, h, w, cin, cout = case
+    nm = "tp%d_%d" % (h, cin)
+    d = {"x": POINT.x(seed, nm + "x", (n, cin, 2, h, w)), "w": POINT.w(0, seed, nm + "w", (cout, cin, 3, 1, 1))}
+    d["s"], d["b"] = POINT.bn(seed, nm + "bn", cout)
+    return d, chain_ref64(d["x"], [(d["w"], ONE, ((1, 0, 0), (1, 0, 0)), d["s"], d["b"], None, True)], dtype)
+
+
+def dual_tensors(dims, c1, c2, cout, stride, seed, nm):
+    n, t, h, w = dims
+    h2, w2 = (h - 1) * stride + 1 + (stride - 1), (w - 1) * stride + 1                  # odd / even source grids
+    d = {"x": POINT.x(seed, nm + "x", (n, c1, t, h, w)), "x2": POINT.x(seed, nm + "x2", (n, c2, t, h2, w2)),
+         "w1": POINT.w(0, seed, nm + "w1", (cout, c1, 1, 1, 1)), "w2": POINT.w(1, seed, nm + "w2", (cout, c2, 1, 1, 1))}
+    d["s1"], d["b1"] = POINT.bn(seed, nm + "bn1", cout)
+    d["s2"], d["b2"] = pow2_scales(cout, (-2, -1)), nonzero_ints(seed, nm + "bn2b", (cout,))
+    return d
+
+
+def dual_reference(case, dtype, seed=41):
+    """PackedConv.call_dual: two 1x1x1 convs on 64 channels summed before the one store."""
+    dims, cout, ld2 = case
+    d = dual_tensors(dims, 64, 64, cout, 1, seed, "du%d_%d" % (dims[2], ld2))
+    raw, a = dual_ref64(d["x"], d["w1"], d["s1"], d["b1"], d["x2"], d["w2"], d["s2"], d["b2"])
+    return d, [_stage(raw, a, 0.25, dtype)]
+
+
+def dual_p8_reference(case, dtype, seed=43):
+    """PackedConv.call_dual_p8: [W1 s1 | W2 s2] as one GEMM over [x ; x2 sampled with the spatial stride]; the scales are folded into the 16-bit weights (a
+    power of two times a small integer: exact)."""
+    dims, c1, c2, cout, stride = case
+    d = dual_tensors(dims, c1, c2, cout, stride, seed, "p8%d_%d" % (dims[2], c1))
+    for k in ("w1", "w2"):
+        ws = d[k] * _chan(d["s" + k[1]]).view(-1, 1, 1, 1, 1)
+        assert all(torch.equal(ws.to(TDT[t]).to(D), ws) for t in TDT)
+    raw, a = dual_ref64(d["x"], d["w1"], d["s1"], d["b1"], d["x2"], d["w2"], d["s2"], d["b2"], stride2=stride)
+    return d, [_stage(raw, a, 0.25, dtype)]
+
+
+def pool_t2_reference(case, dtype, seed=47):
+    """PackedConv.call_pool_t2: 1x1x1 conv + BN (+ residual) + ReLU + the max over frame pairs. Returns the stage before the max and the one after it."""
+    dims, cin, cout, use_res = case
+    n, t, h, w = dims
+    nm = "pt%d_%d" % (h, cin)
+    d = {"x": POINT.x(seed, nm + "x", (n, cin, t, h, w)), "w": POINT.w(0, seed, nm + "w", (cout, cin, 1, 1, 1)), "s": pow2_scales(cout),
+         "b": negative_ints(seed, nm + "b", (cout,), lo=-32), "res": nonzero_ints(seed, nm + "r", (n, cout, t, h, w)) if use_res else None}
+    st = chain_ref64(d["x"], [(d["w"], ONE, P0, d["s"], d["b"], d["res"], True)], dtype)[0]
+    return d, [st, dict(st, y=pair_max_t(st["y"]), raw=pair_max_t(st["raw"]))]
+
+
+def stem_reference(case, dtype, seed=53, lit=0.55, lo=-2):
+    """engine.StemPT: conv 5x7x7 / 2 / pad (2, 3, 3) + BN + ReLU on an integer clip, the max over output-frame pairs, the (1, 3, 3) / (1, 2, 2) max pool.
+    Returns the tensors and three stages: the conv, the pair max (StemPT.conv), the pooled tensor (conv_pool, conv_pool_clip); a max of exact values is exact,
+    and rounding is monotonic: max then round = round then max. The clip is zero beyond the first `lit` of its longer spatial axis and every shift is negative,
+    so there the ReLU yields whole zero pool windows: the pooled output too keeps a quarter of zeros (a max over 18 independent values would keep none), and an
+    epilogue that lost its ReLU shows in all three."""
+    n, c, t, h, w = case
+    nm = "st%d_%d" % (h, w)
+    clip = STEM.x(seed, nm + "x", case)
+    if h >= w:
+        clip[:, :, :, int(lit * h):] = 0.0
+    else:
+        clip[..., int(lit * w):] = 0.0
+    d = {"clip": clip, "w": STEM.w(0, seed, nm + "w", (64, c, 5, 7, 7)), "s": pow2_scales(64), "b": negative_ints(seed, nm + "b", (64,), lo=lo)}
+    st = chain_ref64(d["clip"], [(d["w"], (2, 2, 2), ((2, 3, 3), (2, 3, 3)), d["s"], d["b"], None, True)], dtype)[0]
+    pair = dict(st, y=pair_max_t(st["y"]), raw=pair_max_t(st["raw"]))
+    pool = dict(pair, y=max_pool_ref64(pair["y"], (1, 3, 3), (1, 2, 2)), raw=max_pool_ref64(pair["raw"], (1, 3, 3), (1, 2, 2)))
+    return d, [st, pair, pool]

@@ -38,17 +38,7 @@ def nc(a):
     return a.buf.double().cpu()[..., a.coff:a.coff + a.c].permute(0, 4, 1, 2, 3)
 
 
-def same(got, want, what, fails=None):
-    """torch.equal, with the count and the first differing index on a mismatch."""
-    msg = R.first_mismatch(got, want)
-    if msg:
-        print("%s: %s" % (what, msg))
-    if fails is not None:
-        if msg:
-            fails.append("%s: %s" % (what, msg))
-        return not msg
-    assert torch.equal(got, want), "%s: %s" % (what, msg)
-    return True
+same = R.same                  # torch.equal, with the count and the first differing index on a mismatch
 
 
 def make_layer(case, w, dtype):

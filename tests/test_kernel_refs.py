@@ -256,3 +256,125 @@ def test_epilogue_case_table_passes_the_gate(case, must):
 def test_patch_cases_cover_one_split_and_several():
     splits = {c.name: c.launch_form()[1] for c in R.WGRAD_PATCH}
     assert min(splits.values()) == 1 and max(splits.values()) >= 3, splits
+
+
+# ---- the exact-arithmetic references and case tables of tests/test_hip_fused_exact.py -----------------------------------------------------------------------
+DT16 = ("f16", "bf16")
+
+
+def test_fused_reference_helpers():
+    assert R.pow2_scales(5).tolist() == [0.5, 0.25, 0.5, 0.25, 0.5]
+    v = R.nonzero_ints(3, "nz", (4096,))
+    assert bool((v != 0).all()) and float(v.min()) == -8 and float(v.max()) == 8 and bool((R.negative_ints(3, "ng", (512,)) < 0).all())
+    assert R.exact_in_fp32_steps(torch.tensor([0.25 * (2 ** 24 - 1)]), 0.25)
+    for bad, step in ((torch.tensor([0.25 * 2 ** 24]), 0.25), (torch.tensor([0.125]), 0.25), (torch.tensor([1.0]), 0.3)):
+        with pytest.raises(AssertionError):
+            R.exact_in_fp32_steps(bad, step)
+    # bf16 keeps 8 bits: 257 -> 256 (a tie, to even, TOWARDS zero), 259 -> 260 (a tie away from zero), 258.5 -> 258 (no tie), 256 stays
+    share, ties = R.rounding_stats(torch.tensor([257.0, 259.0, 258.5, 256.0], dtype=D), "bf16")
+    assert share == 0.75 and ties == 1
+    assert R.rounding_stats(torch.tensor([2049.0, 2051.0, 2048.5, 3.0], dtype=D), "f16") == (0.75, 1)      # 2048.5 is not on the f16 grid, not a tie either
+    y = torch.arange(2 * 3 * 5 * 2 * 2, dtype=D).reshape(2, 3, 5, 2, 2)
+    assert torch.equal(R.pair_max_t(y), y[:, :, [1, 3]]) and R.upsample2x_nchw(y).shape == (2, 3, 5, 4, 4)
+    assert torch.equal(R.upsample2x_nchw(y)[0, 0, 0], torch.tensor([[0.0, 0, 1, 1], [0, 0, 1, 1], [2, 2, 3, 3], [2, 2, 3, 3]], dtype=D))
+    assert torch.equal(R.max_pool_ref64(y, (1, 2, 2), (1, 2, 2))[..., 0, 0], y[..., 1, 1])
+    assert R.bn_is_telling(R.pow2_scales(8), R.nonzero_ints(3, "b", (8,)))
+    for s, b in ((torch.ones(8), torch.ones(8)), (R.pow2_scales(8) * 3, torch.ones(8)), (R.pow2_scales(8), torch.zeros(8)), (R.pow2_scales(8), torch.full((8,), 0.5))):
+        with pytest.raises(AssertionError):
+            R.bn_is_telling(s, b)
+
+
+def test_chain_and_dual_references_vs_explicit_taps():
+    """chain_ref64 against the tap-by-tap conv with the rounding done by hand; dual_ref64 against two such convs; the step of each stage."""
+    x = R.small_ints(5, "cx", (2, 6, 2, 5, 6), lo=-8, hi=8, density=1.0)
+    w1, w2 = R.small_ints(5, "cw1", (4, 6, 1, 3, 3), lo=-16, hi=16, density=1.0), R.small_ints(5, "cw2", (6, 4, 1, 1, 1))
+    s1, b1, s2, b2 = R.pow2_scales(4), R.nonzero_ints(5, "cb1", (4,)), R.pow2_scales(6), R.nonzero_ints(5, "cb2", (6,))
+    st = R.chain_ref64(x, [(w1, R.ONE, R.P011, s1, b1, None, True), (w2, R.ONE, R.P0, s2, b2, x, True)], "bf16")
+    ch = lambda v: v.view(1, -1, 1, 1, 1)
+    m = (_conv_taps(x, w1, (1, 1, 1), (0, 1, 1), (0, 1, 1)) * ch(s1) + ch(b1)).clamp_min(0)
+    assert torch.equal(st[0]["raw"], m) and st[0]["step"] == 0.25 and st[1]["step"] == 0.0625
+    m16 = m.to(torch.bfloat16).to(D)
+    assert not torch.equal(m16, m) and torch.equal(st[0]["y"], m16)
+    out = (_conv_taps(m16, w2, (1, 1, 1), (0, 0, 0), (0, 0, 0)) * ch(s2) + ch(b2) + x).clamp_min(0)
+    assert torch.equal(st[1]["raw"], out) and torch.equal(st[1]["y"], out.to(torch.bfloat16).to(D))
+    assert torch.equal(st[1]["abs"], _conv_taps(m16, w2.abs(), (1, 1, 1), (0, 0, 0), (0, 0, 0)) * ch(s2) + ch(b2.abs()) + x.abs())
+    fp = R.chain_ref64(x, [(w1, R.ONE, R.P011, s1, b1, None, False)], "bf16", fp32_out=True)[0]
+    assert torch.equal(fp["y"], fp["raw"]) and bool((fp["y"] < 0).any()) and not fp["stored16"]
+    x2 = R.small_ints(5, "cx2", (2, 4, 2, 9, 11))
+    wd = R.small_ints(5, "cwd", (4, 4, 1, 1, 1))
+    raw, a = R.dual_ref64(x, w1[:, :, :, 1:2, 1:2], s1, b1, x2, wd, s1.flip(0), b1, stride2=2, relu=True)
+    want = _conv_taps(x, w1[:, :, :, 1:2, 1:2], (1, 1, 1), (0, 0, 0), (0, 0, 0)) * ch(s1) + ch(b1) + _conv_taps(x2[:, :, :, ::2, ::2], wd, (1, 1, 1), (0, 0, 0), (0, 0, 0)) * ch(s1.flip(0)) + ch(b1)
+    assert torch.equal(raw, want.clamp_min(0)) and bool((a >= want.abs()).all())
+
+
+def _table_rounds(results, table_name):
+    """Condition 4 over a table: for each type, a case whose every intermediate is rounded (>= 1 %, ties to even towards zero among them)."""
+    for dt in DT16:
+        assert any(ok for d, ok in results if d == dt), "%s: no %s case rounds every intermediate" % (table_name, dt)
+
+
+def _mix_promise(mix, stats, dt, n_inter):
+    ok = all(R.rounding_happens(stats, i) for i in range(n_inter))
+    assert ok or dt not in mix.rounds
+    return ok
+
+
+def test_bneck_frame_case_table_meets_the_conditions():
+    assert [(c.temporal, c.n, c.t) for c in R.BNECK_FRAME_CASES] == [(False, 1, 3), (False, 3, 2), (True, 2, 2), (True, 1, 2)]
+    results = []
+    for c in R.BNECK_FRAME_CASES:
+        x, ws, bn = c.tensors()
+        assert all(R.bn_is_telling(s, b) for s, b in bn) and float(x.abs().max()) == c.mix.x_hi and torch.equal(x, x.round())
+        for dt in DT16:
+            stats = R.fused_conditions(R.chain_ref64(x, c.stages(x, ws, bn), dt), dt, "bneck_frame " + c.name, c.mix)
+            results.append((dt, _mix_promise(c.mix, stats, dt, 2)))
+    _table_rounds(results, "BNECK_FRAME_CASES")
+
+
+@pytest.mark.parametrize("table", ["BNECK_TAIL64_CASES", "BNECK_TAIL128_CASES"])
+def test_bneck_tail_case_tables_meet_the_conditions(table):
+    cases = getattr(R, table)
+    want = [(2, 3, 7, 9), (1, 1, 16, 16), (3, 6, 9, 11), (1, 2, 20, 55)] if table.endswith("64_CASES") else [(2, 3, 7, 9), (1, 1, 16, 16), (4, 2, 14, 30)]
+    assert [c.dims for c in cases] == want
+    forms, results = set(), []
+    for c in cases:
+        d = c.tensors()
+        assert R.bn_is_telling(d["s2"], d["b2"]) and R.bn_is_telling(d["s3"], d["b3"]) and bool((d["res"] != 0).all())
+        if c.cmid == 64:
+            assert R.bn_is_telling(d["sd"], d["bd"]) and not torch.equal(d["sd"], d["s3"])
+        forms |= set(c.forms)
+        for dt in DT16:
+            for form, st in c.reference(d, dt).items():
+                stats = R.fused_conditions(st, dt, "bneck_tail %s %s" % (c.name, form), c.mix)
+                results.append((dt, _mix_promise(c.mix, stats, dt, 1)))
+    assert forms == ({"residual", "dual", "pool"} if table.endswith("64_CASES") else {"residual"})
+    _table_rounds(results, table)
+
+
+def test_unetpp_tail_case_table_meets_the_conditions():
+    assert [(c.h, c.w) for c in R.UPP_TAIL_CASES[:4]] == [(16, 16), (18, 34), (48, 80), (2, 2)] and R.UPP_TAIL_CASES[2].n == 3
+    assert R.UPP_TAIL_CASES[0].npatch == 1 and all(c.npatch > 2 * 256 for c in R.UPP_TAIL_CASES if c.walk) and any(c.walk for c in R.UPP_TAIL_CASES)
+    results = []
+    for c in R.UPP_TAIL_CASES:
+        d = c.tensors()
+        assert R.bn_is_telling(d["s1"], d["b1"]) and R.bn_is_telling(d["s2"], d["b2"]) and R.bn_is_telling(None, d["bias"])
+        for dt in DT16:
+            st = c.reference(d, dt)
+            assert tuple(st[2]["y"].shape) == (c.n, 3, 1, c.h, c.w) and not st[2]["stored16"]
+            stats = R.fused_conditions(st, dt, "unetpp_tail " + c.name, c.mix)
+            results.append((dt, _mix_promise(c.mix, stats, dt, 2)))
+    _table_rounds(results, "UPP_TAIL_CASES")
+
+
+@pytest.mark.parametrize("fn,table", [("tpair_reference", "TPAIR_CASES"), ("dual_reference", "DUAL_CASES"), ("dual_p8_reference", "DUAL_P8_CASES"),
+                                      ("pool_t2_reference", "POOL_T2_CASES"), ("stem_reference", "STEM_CASES")])
+def test_single_stage_case_tables_meet_the_conditions(fn, table):
+    """No 16-bit intermediate: conditions 1, 2, 3 and 5 on every stage, the pair max and the pooled stem output included."""
+    for c in getattr(R, table):
+        for dt in DT16:
+            d, st = getattr(R, fn)(c, dt)
+            R.fused_conditions(st, dt, "%s %s" % (table, c))
+            assert all(x["relu"] for x in st)
+            for s, b in (("s", "b"), ("s1", "b1"), ("s2", "b2")):
+                if s in d:
+                    assert R.bn_is_telling(d[s], d[b])
