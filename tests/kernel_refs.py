@@ -1,6 +1,7 @@
 """float64 references of the memory-bound training kernels (csrc/train_ops.hip, the idx / backward half of csrc/pool_layout.hip, csrc/head.hip, csrc/loss.hip)
 and the two value generators their tests use; then the exact-arithmetic conv references and case tables of tests/test_hip_conv_exact.py and, at the end, the chain
-references, input conditions and case tables of the fused forward kernels (tests/test_hip_fused_exact.py). A plain helper module: tests/test_kernel_refs.py checks every reference here against float64 torch (autograd) on
+references, input conditions and case tables of the fused forward kernels (tests/test_hip_fused_exact.py), then the case table of the plain forward conv and the launcher's
+acceptance rule per tile configuration (fwd_accepts; tests/test_hip_conv_fwd_exact.py). A plain helper module: tests/test_kernel_refs.py checks every reference here against float64 torch (autograd) on
 the CPU, the -m gpu op tests (test_hip_train_kernels.py, test_hip_head_ops.py, test_hip_losses.py) compare the kernels with them.
 
 Activations are channels-last: (pixels, C) for the BatchNorm kernels, (n, t, h, w, c) for the pools, (n, h, w, c) for the resizes. Everything returned is a
@@ -868,3 +869,292 @@ def stem_reference(case, dtype, seed=53, lit=0.55, lo=-2):
     pair = dict(st, y=pair_max_t(st["y"]), raw=pair_max_t(st["raw"]))
     pool = dict(pair, y=max_pool_ref64(pair["y"], (1, 3, 3), (1, 2, 2)), raw=max_pool_ref64(pair["raw"], (1, 3, 3), (1, 2, 2)))
     return d, [st, pair, pool]
+
+
+# ---- the plain forward conv under every tile configuration (tests/test_hip_conv_fwd_exact.py) ------------------------------------------------------------------
+# One single-stage chain per row: integer x and w, power-of-two scales, non-zero integer shifts, ReLU; every live tile configuration that takes the row must equal
+# chain_ref64 bit for bit, and must take it exactly where fwd_accepts -- the launcher's acceptance rule restated from the code -- says so.
+def cl(t, dtype, ld=None, coff=0, seed=0):
+    """(n, c, t, h, w) float64 cpu -> channels-last Act on the GPU; with `ld`: a slice [coff, coff + c) of a wider buffer whose other channels hold
+    non-zero integers (a kernel that reads past its slice picks them up)."""
+    from ted_spad_amd import engine as E
+    v = t.permute(0, 2, 3, 4, 1).contiguous()
+    c = v.shape[-1]
+    if ld is None:
+        return E.Act(v.to(TDT[dtype]).cuda(), c)
+    buf = small_ints(seed, "slicefill", tuple(v.shape[:4]) + (ld,), lo=1, hi=3, density=1.0)
+    buf[..., coff:coff + c] = v
+    return E.Act(buf.to(TDT[dtype]).cuda(), c, coff)
+
+
+def nc(a):
+    """Act -> (n, c, t, h, w) float64 cpu."""
+    return a.buf.double().cpu()[..., a.coff:a.coff + a.c].permute(0, 4, 1, 2, 3)
+
+
+NUM_TILE_CFGS = 40                         # conv_igemm.hip NUM_CFGS; the GPU file checks it against tedspad_conv_num_tile_cfgs()
+RETIRED_CFGS = (15, 16, 37, 39)
+LIVE_CFGS = tuple(c for c in range(1, NUM_TILE_CFGS + 1) if c not in RETIRED_CFGS)
+KTAB_MAX_BYTES, KTAB_SMALL_BYTES, LDS_LIMIT = 10240, 1024, 160 * 1024       # conv_common.h; launch.h raise_lds
+# conv_igemm.hip launch_cfg: the K-table bytes KT of every generic tile (0: table-free), the (FR, KS, TW) of the stem halo tiles, narrow_sibling
+GENERIC_KT = {1: KTAB_MAX_BYTES, 2: KTAB_MAX_BYTES, 3: KTAB_MAX_BYTES, 4: KTAB_MAX_BYTES, 5: KTAB_MAX_BYTES, 6: KTAB_SMALL_BYTES, 7: KTAB_SMALL_BYTES,
+              8: KTAB_SMALL_BYTES, 10: KTAB_SMALL_BYTES, 11: KTAB_MAX_BYTES, 12: KTAB_MAX_BYTES, 13: KTAB_MAX_BYTES, 14: KTAB_MAX_BYTES, 17: 0, 18: 0,
+              22: KTAB_MAX_BYTES, 23: 0, 24: KTAB_MAX_BYTES, 35: 0, 36: 0}
+STEM_TILES = {9: (1, 1, 32), 20: (2, 1, 32), 21: (1, 2, 32), 29: (1, 1, 16), 30: (1, 2, 16), 31: (2, 1, 16)}
+NARROW_SIBLING = {1: 2, 24: 2, 3: 4, 6: 7, 11: 12, 13: 14, 22: 14, 18: 17, 23: 17, 35: 17, 36: 17}
+SPLIT_K_TILES = (22, 23, 24, 35, 36)
+FWD_EXTRAS = ("mask", "y32", "stats", "ostrided", "gathered")       # + ("stats_rows", rows) for grouped statistics
+
+
+class FwdGeo:
+    """A ConvCase as tedspad_conv_fwd_ex sees it (conv_fwd_impl's ConvKP): kernel-form channels, kernel, strides and front pads, the padded K, the output rows."""
+
+    def __init__(self, case, n=None):
+        self.cin, self.k, self.stride, self.pf, self.thw = case.kernel_geometry()
+        self.n, self.out, self.cout = case.dims[0] if n is None else n, tuple(case.out), (case.cout + 7) // 8 * 8
+        self.kpad = (self.k[0] * self.k[1] * self.k[2] * self.cin + 63) // 64 * 64
+        self.nk, self.utap = self.kpad // 64, self.cin % 64 == 0
+        self.M = self.n * self.out[0] * self.out[1] * self.out[2]
+        self.pointwise = self.k == (1, 1, 1) and self.stride == (1, 1, 1) and self.pf == (0, 0, 0) and self.out == tuple(self.thw)
+        self.same, self.stride1 = self.out == tuple(self.thw), self.stride == (1, 1, 1)
+
+    def with_cout(self, cout):
+        g = FwdGeo.__new__(FwdGeo)
+        g.__dict__.update(self.__dict__)
+        g.cout = cout
+        return g
+
+
+def _extras(extras):
+    names = set(e if isinstance(e, str) else e[0] for e in extras)
+    assert names <= set(FWD_EXTRAS) | {"stats_rows"}, names
+    rows = next((e[1] for e in extras if not isinstance(e, str)), 0)
+    if rows:
+        names.add("stats")
+    return names, rows
+
+
+def fwd_refusals_one(cfg, g, extras=()):
+    """Every clause of ONE launch's acceptance rule that the geometry `g` (a FwdGeo) fails under the forced tile `cfg`, by name ([]: the tile takes it)."""
+    ex, rows = _extras(extras)
+    kt, kh, kw = g.k
+    T, H, W = g.thw
+    plain = not (ex & {"mask", "y32", "stats", "ostrided"})
+    bad = []
+    # conv_fwd_impl, before any tile is looked at: statistics groups of >= 256 rows; gathered sources on the chunk-major halo tiles only
+    if rows and rows < 256:
+        bad.append("stats_rows<256")
+    if "gathered" in ex:
+        if cfg not in (32, 33, 38, 39, 40):
+            bad.append("gathered:tile")
+        if kt != 1 or g.cin % 64 or g.cin // 64 > 8:
+            bad.append("gathered:geometry")
+    if cfg in RETIRED_CFGS or not 1 <= cfg <= NUM_TILE_CFGS:       # launch_cfg: case 15 / 16 / 37 / 39
+        return bad + ["retired"]
+    if cfg in GENERIC_KT:      # launch<>: `if (KT == 0 ? !p.utap : p.Kpad > KT)`; the generic kernel has every epilogue and, with one K tile, a split-K tile's second wave set multiplies its half of it
+        KT = GENERIC_KT[cfg]
+        if KT == 0 and not g.utap:
+            bad.append("generic:cin%64")
+        if KT and g.kpad > KT:
+            bad.append("generic:kpad>%d" % KT)
+    elif cfg in STEM_TILES:      # conv_fwd_impl `if (cfg == 9 || ...)` and launch_stem_halo
+        FR, KS, TW = STEM_TILES[cfg]
+        if g.cin != 8:
+            bad.append("stem:cin!=8")
+        if ex & {"mask", "y32", "ostrided"}:
+            bad.append("stem:extras")
+        if rows and rows % (g.out[0] * g.out[1] * g.out[2]):
+            bad.append("stem:stats_rows")
+        if g.cout > 64:
+            bad.append("stem:cout>64")
+        if g.stride[2] != 1:
+            bad.append("stem:sw!=1")
+        if g.kpad > 8 * 256 * 8:
+            bad.append("stem:kpad")
+        TH = 256 // TW
+        HH, WH, HT = (TH - 1) * g.stride[1] + kh, (TW - 1) * g.stride[2] + kw, kt + (FR - 1) * g.stride[0]
+        P = HT * HH * WH
+        main = (P + 63) // 64 * 64 * 16 + (2 if FR == 1 else 4) * 8192 + g.nk * 32
+        if max(main, 256 * FR * 68 * 4) > LDS_LIMIT:
+            bad.append("stem:lds")
+    elif cfg == 19:            # conv_pw.hip launch_conv_pw
+        if not g.pointwise or g.cin not in (64, 128) or g.kpad != g.cin:
+            bad.append("pw:geometry")
+        if not plain:
+            bad.append("pw:extras")
+    elif cfg in (25, 26):      # conv_p8.hip launch_conv_p8
+        if not g.utap:
+            bad.append("p8:cin%64")
+        if g.nk < 2:
+            bad.append("p8:nk<2")
+        if g.cout % 256:
+            bad.append("p8:cout%256")
+        if not plain:
+            bad.append("p8:extras")
+    elif cfg == 27:            # conv_flat.hip launch_conv_flat, launch_flat_t
+        same = g.same and g.pf[0] == 0 and g.pf[1] < kh and g.pf[2] < kw
+        if g.cin != 64 or kt != 1 or not g.stride1 or not same or not 2 <= kh * kw <= 32 or g.kpad != kh * kw * 64:
+            bad.append("flat:geometry")
+        if g.cout > 64:
+            bad.append("flat:cout>64")
+        if not plain:
+            bad.append("flat:extras")
+        S = (256 + (kh - 1) * W + (kw - 1) + 1) * 8
+        if max((S + 63) // 64 * 64 * 16 + 3 * 8192, 256 * 68 * 4) > LDS_LIMIT:
+            bad.append("flat:lds")
+    elif cfg in (28, 34):      # conv_flat.hip launch_conv_tflat; conv_patch.hip launch_conv_patch, mode 2 (its halo, T * (256 / T) positions, always fits)
+        same = g.same and g.pf[1] == 0 and g.pf[2] == 0 and g.pf[0] < kt
+        if g.cin % 64 or kh != 1 or kw != 1 or not 2 <= kt <= 3 or not g.stride1 or not same or g.kpad != kt * g.cin:
+            bad.append("temporal:geometry")
+        if T > 4:
+            bad.append("temporal:T>4")
+        if g.cout > (64 if cfg == 28 else 512):
+            bad.append("temporal:cout")
+        if (not plain) if cfg == 28 else ("ostrided" in ex):
+            bad.append("temporal:extras")
+    elif cfg in (32, 33):      # conv_patch.hip launch_conv_patch, modes 0 / 1; launch_patch_t (the head / tail split changes no clause: none depends on cout <= 512)
+        same = g.same and g.pf[0] < kt and g.pf[1] < kh and g.pf[2] < kw
+        kt_ok = g.pf[0] == 0 if kt == 1 else (kt <= 3 and T * H * W * g.cin * g.n < 2 ** 31)
+        if g.cin % 64 or not kt_ok or not g.stride1 or not same or not 2 <= kh * kw <= 16 or g.kpad != kt * kh * kw * g.cin:
+            bad.append("patch:geometry")
+        if g.cout > 512:
+            bad.append("patch:cout>512")
+        if "ostrided" in ex:
+            bad.append("patch:extras")
+        NP = (16 + kh - 1) * (16 + kw - 1) if cfg == 32 else 256 + (kh - 1) * W + (kw - 1)
+        S = (NP + (1 if cfg == 33 else 0)) * 8
+        if ((S + 63) // 64 * 64 + 255) // 256 > 12:
+            bad.append("patch:halo>384")
+    elif cfg in (38, 40):      # conv_patch.hip launch_conv_patch2; conv_patch3.hip launch_conv_patch3 (cout = 128: two launches of 64), launch_conv_patch3_64
+        if (g.cin % (64 if "gathered" in ex else 32) or g.k != (1, 3, 3) or g.pf != (0, 1, 1) or not g.stride1 or not g.same or g.kpad < 9 * g.cin):
+            bad.append("patch2:geometry")
+        if "ostrided" in ex:
+            bad.append("patch2:extras")
+        if cfg == 40:
+            if not (32 < g.cout <= 64 or g.cout == 128):
+                bad.append("patch3:cout")
+            if "gathered" in ex and (g.cin <= 64 or "stats" in ex):
+                bad.append("patch3:gathered")
+    else:
+        raise AssertionError(cfg)
+    return bad
+
+
+def fwd_refusals(cfg, case, extras=(), n=None):
+    """The failed clauses of PackedConv.__call__ on `case` under the forced tile `cfg`. launch_cfg: cout = 128 k + r with 0 < r <= 64 on a tile with a 64-wide sibling
+    runs the last r channels on the sibling first; if the sibling declines them, the conv goes unsplit; if it takes them, the head's verdict is the call's."""
+    g = FwdGeo(case, n)
+    sib = NARROW_SIBLING.get(cfg, 0)
+    if sib and "gathered" not in _extras(extras)[0] and g.cout > 128 and 0 < g.cout % 128 <= 64:
+        head = g.cout // 128 * 128
+        if not fwd_refusals_one(sib, g.with_cout(g.cout - head), extras):
+            return fwd_refusals_one(cfg, g.with_cout(head), extras)
+    return fwd_refusals_one(cfg, g, extras)
+
+
+def fwd_accepts(cfg, case, extras=()):
+    """The launcher's acceptance rule for a forced tile, restated from the code's own formulas (as wgrad_form does for the weight gradient)."""
+    return not fwd_refusals(cfg, case, extras)
+
+
+def fwd_is_split(cfg, case):
+    """launch_cfg runs the row as a head on `cfg` and a tail on its 64-wide sibling."""
+    g = FwdGeo(case)
+    sib = NARROW_SIBLING.get(cfg, 0)
+    return bool(sib) and g.cout > 128 and 0 < g.cout % 128 <= 64 and not fwd_refusals_one(sib, g.with_cout(g.cout % 128))
+
+
+FWD_SMALL = Mix(2, 0.5, [(2, 0.5)])
+FWD_BIG = Mix(8, 0.5, [(32, 0.5)])
+
+
+class FwdCase:
+    """A FWD_CASES row: the conv and its options. big: x in [-8, 8], w in [-32, 32] (otherwise both in [-2, 2]), density 0.5 either way; residual: integers in
+    [-8, 8]; slices: the row also runs on channel slices of wider buffers; rounds: the types whose store the row must really round (condition 4)."""
+
+    def __init__(self, conv, big=False, residual=False, slices=False, rounds=()):
+        self.conv, self.name, self.big, self.residual, self.slices = conv, conv.name, big, residual, slices
+        self.mix, self.rounds = FWD_BIG if big else FWD_SMALL, tuple(rounds)
+        self.stem = conv.kernel_geometry()[0] == 8
+
+    def tensors(self, seed=61):
+        c, m = self.conv, self.mix
+        n, t, h, w = c.dims
+        d = {"x": m.x(seed, c.name + "x", (n, c.cin, t, h, w)), "w": m.w(0, seed, c.name + "w", (c.cout, c.cin) + c.k)}
+        d["s"], d["b"] = m.bn(seed, c.name + "bn", c.cout)
+        d["res"] = small_ints(seed, c.name + "r", (n, c.cout) + c.out, lo=-8, hi=8, density=1.0) if self.residual else None
+        return d
+
+    def stage(self, d):
+        c = self.conv
+        return (d["w"], c.stride, (c.pf, c.pb), d["s"], d["b"], d["res"], True)
+
+
+_FWD_REF = {}
+
+
+def fwd_reference(case, dtype):
+    """(tensors, [stage]) of a FwdCase: chain_ref64 with a single stage, rounded once. The float64 convs are computed once per row and shared by both types."""
+    if case.name not in _FWD_REF:
+        d = case.tensors()
+        _FWD_REF[case.name] = (d, chain_ref64(d["x"], [case.stage(d)], "f16")[0])
+    d, st = _FWD_REF[case.name]
+    return d, [dict(st, y=round_once(st["raw"], dtype))]
+
+
+def fwd_stats_reference(case, d):
+    """(z, per-sample statistics (n, 2, c), step) of a stem row: z = scale * conv + shift before the residual and the ReLU; the gate on the absolute sums in steps."""
+    c = case.conv
+    _, z = conv_fwd_ref64(d["x"], d["w"], c.stride, c.pf, c.pb, scale=d["s"], shift=d["b"])
+    _, zabs = conv_fwd_ref64(d["x"].abs(), d["w"].abs(), c.stride, c.pf, c.pb, scale=d["s"], shift=d["b"].abs())
+    step = float(d["s"].abs().min())
+    sabs = conv_stats_ref64(z.abs(), 1)[0]             # every partial sum of z and of z^2 is bounded by the sums of |z| and z^2
+    assert exact_in_fp32(sabs[0] / step, sabs[1] / step ** 2, stats_z=zabs / step)
+    return z, conv_stats_ref64(z, c.dims[0]), step
+
+
+FWD_CASES = [
+    FwdCase(ConvCase("pw_64_136_res", (2, 2, 9, 7), 64, 136, (1, 1, 1)), residual=True),                           # Kpad 64: one K tile, M = 252 < 256, sibling split r = 8; tile 19
+    FwdCase(ConvCase("pw_128_256_s2", (2, 2, 15, 14), 128, 256, (1, 1, 1), S2)),                                   # the shortest K the ping-pong takes, strided gather on 25 / 26
+    FwdCase(ConvCase("pw_192_256", (1, 1, 5, 7), 192, 256, (1, 1, 1)), slices=True),                               # odd K-tile count, M = 35
+    FwdCase(ConvCase("pw_1024_64", (1, 2, 5, 7), 1024, 64, (1, 1, 1))),                                            # Kpad = 1024: the short-K tiles 6, 7, 8, 10 take it ...
+    FwdCase(ConvCase("pw_1088_64", (1, 2, 5, 7), 1088, 64, (1, 1, 1))),                                            # ... and refuse Kpad = 1088
+    FwdCase(ConvCase("t3_T4_256_64", (3, 4, 9, 11), 256, 64, (3, 1, 1))),                                          # tiles 28 and 34 at T = 4
+    FwdCase(ConvCase("t3_T3_64_48_res", (2, 3, 5, 13), 64, 48, (3, 1, 1)), residual=True, slices=True),            # T = 3 (an idle wave), ragged cout
+    FwdCase(ConvCase("t3_T2_128_512_res", (2, 2, 9, 11), 128, 512, (3, 1, 1)), big=True, residual=True, rounds=("bf16",)),      # two 256-channel tiles on 25 / 26, tile 34 at cout = 512
+    FwdCase(ConvCase("t3_2048_512", (2, 2, 7, 7), 2048, 512, (3, 1, 1)), big=True, rounds=BOTH),                   # K = 6144: 96 K tiles
+    FwdCase(ConvCase("t5_kmax_2048_64", (1, 5, 3, 3), 2048, 64, (5, 1, 1))),                                       # Kpad = 10240 = KTAB_MAX_BYTES: a full K table
+    FwdCase(ConvCase("k333_s2_tfsame", (2, 4, 9, 9), 64, 64, (3, 3, 3), (2, 2, 2), pf=(0, 1, 1), pb=(1, 1, 1))),   # asymmetric pads, strided in all three dims
+    FwdCase(ConvCase("s2_3x3_128_128", (2, 2, 15, 15), 128, 128, (1, 3, 3), S2)),                                  # M = 256 exactly
+    FwdCase(ConvCase("3x3_64_40_res", (1, 2, 9, 7), 64, 40, (1, 3, 3)), big=True, residual=True, slices=True, rounds=BOTH),     # frames smaller than a tile on 27, 32, 33, 38, 40
+    FwdCase(ConvCase("3x3_256_256", (3, 2, 14, 13), 256, 256, (1, 3, 3)), big=True, rounds=BOTH),                  # 36 K tiles on 25 / 26, ragged M
+    FwdCase(ConvCase("k333_96_208_res", (1, 4, 9, 10), 96, 208, (3, 3, 3)), residual=True),                        # cin % 64 != 0 (table tiles only), r = 80 > 64: unsplit
+    FwdCase(ConvCase("k333_144_288", (1, 2, 7, 9), 144, 288, (3, 3, 3)), big=True, rounds=("bf16",)),              # sibling split r = 32 on every 128-wide tile, split-K ones included
+    FwdCase(ConvCase("k333_64_192", (2, 3, 9, 17), 64, 192, (3, 3, 3)), big=True, rounds=BOTH),                    # patch and flat tiles 32 / 33 with temporal taps, ragged patches
+    FwdCase(ConvCase("unet_first_3_64", (3, 1, 20, 37), 3, 64, (1, 3, 3))),                                        # stem halo tiles on K = 72
+    FwdCase(ConvCase("stem_large", (2, 8, 32, 32), 3, 64, (5, 7, 7), (2, 2, 2), pf=(2, 3, 3), pair_w=3)),          # the six stem tiles on the largei3d stem
+    FwdCase(ConvCase("stem_i3d", (2, 8, 32, 32), 3, 64, (7, 7, 7), (2, 2, 2), pf=(2, 2, 2), pb=(3, 3, 3), pair_w=2)),           # ... on the Inception stem, TF-SAME pads
+    FwdCase(ConvCase("k13_64_64", (2, 2, 5, 9), 64, 64, (1, 1, 3))),                                               # a second kernel shape for tile 27 (and 32 / 33): 1 x 1 x 3
+    FwdCase(ConvCase("t2_T3_128_64", (2, 3, 5, 9), 128, 64, (2, 1, 1), pf=(1, 0, 0), pb=(0, 0, 0))),               # ... for tiles 28 and 34: 2 x 1 x 1, the pad in front
+] + [FwdCase(c) for c, _ in EPILOGUE_CASES]                                                                         # the three epilogue rows with the plain epilogue
+FWD_STEM_ROWS = [c for c in FWD_CASES if c.stem]
+FWD_SLICE_ROWS = [c for c in FWD_CASES if c.slices]
+SINGLE_CLASS_TILES = {19: ((1, 1, 1), (1, 1, 1)), 38: ((1, 3, 3), (1, 1, 1)), 40: ((1, 3, 3), (1, 1, 1))}      # launchers that admit one (kernel, stride) only
+GATHER_FWD_CASES = [((2, 1, 12, 20), (64, 64), 64), ((2, 1, 28, 28), (128, 64, 64), 128), ((1, 1, 2, 2), (64, 128), 24)]       # dims, source channels, cout (1 x 3 x 3)
+
+
+def gather_conv_case(row):
+    dims, chans, cout = row
+    return ConvCase("gather_%dx%d_%d" % (dims[2], dims[3], cout), dims, sum(chans), cout, (1, 3, 3))
+
+
+def gather_fwd_reference(row, dtype, seed=67):
+    """PackedConv.gather on a GATHER_FWD_CASES row: the sources (n, c_i, t, h, w) -- source 0 at half the height and width --, w, scale, shift, and chain_ref64's
+    single stage on the concatenation built in float64 (source 0 through the x2 nearest map)."""
+    dims, chans, cout = row
+    n, t, h, w = dims
+    name = gather_conv_case(row).name
+    srcs = [small_ints(seed, "%s_x%d" % (name, i), (n, ci, t) + ((h // 2, w // 2) if i == 0 else (h, w)), density=0.5) for i, ci in enumerate(chans)]
+    x = torch.cat([upsample2x_nchw(srcs[0])] + srcs[1:], dim=1)
+    d = {"srcs": srcs, "w": small_ints(seed, name + "w", (cout, sum(chans), 1, 3, 3), density=0.5), "s": pow2_scales(cout), "b": nonzero_ints(seed, name + "b", (cout,))}
+    return d, chain_ref64(x, [(d["w"], ONE, P011, d["s"], d["b"], None, True)], dtype)

@@ -20,24 +20,7 @@ SENTINEL = 12345.0
 GUARD = 64                     # floats in front of and behind the accumulator (256 bytes: keeps its alignment)
 
 
-def cl(t, dtype, ld=None, coff=0, seed=0):
-    """(n, c, t, h, w) float64 cpu -> channels-last Act on the GPU; with `ld`: a slice [coff, coff + c) of a wider buffer whose other channels hold
-    non-zero integers (a kernel that reads past its slice picks them up)."""
-    from ted_spad_amd import engine as E
-    v = t.permute(0, 2, 3, 4, 1).contiguous()
-    c = v.shape[-1]
-    if ld is None:
-        return E.Act(v.to(R.TDT[dtype]).cuda(), c)
-    buf = R.small_ints(seed, "slicefill", tuple(v.shape[:4]) + (ld,), lo=1, hi=3, density=1.0)
-    buf[..., coff:coff + c] = v
-    return E.Act(buf.to(R.TDT[dtype]).cuda(), c, coff)
-
-
-def nc(a):
-    """Act -> (n, c, t, h, w) float64 cpu."""
-    return a.buf.double().cpu()[..., a.coff:a.coff + a.c].permute(0, 4, 1, 2, 3)
-
-
+cl, nc = R.cl, R.nc           # (n, c, t, h, w) float64 <-> channels-last Act, with channel slices of wider buffers: shared with the other exact-arithmetic files
 same = R.same                  # torch.equal, with the count and the first differing index on a mismatch
 
 

@@ -378,3 +378,87 @@ def test_single_stage_case_tables_meet_the_conditions(fn, table):
             for s, b in (("s", "b"), ("s1", "b1"), ("s2", "b2")):
                 if s in d:
                     assert R.bn_is_telling(d[s], d[b])
+
+
+# ---- the forward conv under every tile configuration: the case table of tests/test_hip_conv_fwd_exact.py ------------------------------------------------------------
+@pytest.mark.parametrize("dtype", R.BOTH)
+@pytest.mark.parametrize("fc", R.FWD_CASES, ids=[c.name for c in R.FWD_CASES])
+def test_fwd_case_table_meets_the_conditions(fc, dtype):
+    """Conditions 1-3 and bn_is_telling on every row; every (input channel, tap) of every row has a non-zero weight, so a dropped tap shows; every 'big' row really
+    rounds in bf16 (>= 1 % of its stores changed, exact ties resolved towards zero among them), rows t3_2048_512, 3x3_256_256, k333_64_192 and 3x3_64_40_res in f16 too."""
+    d, ref = R.fwd_reference(fc, dtype)
+    assert R.bn_is_telling(d["s"], d["b"])
+    stats = R.fused_conditions(ref, dtype, "fwd " + fc.name)
+    assert bool((d["w"] != 0).any(0).all()), "a tap of an input channel has no weight"
+    assert fc.big == ("bf16" in fc.rounds) and set(fc.rounds) <= set(R.BOTH)
+    if dtype in fc.rounds:
+        assert R.rounding_happens(stats, 0), (fc.name, dtype, stats)
+    assert (fc.residual, d["res"] is not None) in ((True, True), (False, False))
+    if fc.stem:
+        R.fwd_stats_reference(fc, d)            # the gate on the statistics' absolute sums and on |z| < 4096 steps
+
+
+def test_fwd_rows_that_must_round_in_f16_too():
+    both = sorted(c.name for c in R.FWD_CASES if c.rounds == R.BOTH)
+    assert both == sorted(["t3_2048_512", "3x3_256_256", "k333_64_192", "3x3_64_40_res"])
+    assert sorted(c.name for c in R.FWD_CASES if c.big) == sorted(both + ["t3_T2_128_512_res", "k333_144_288"])
+
+
+@pytest.mark.parametrize("dtype", R.BOTH)
+@pytest.mark.parametrize("row", R.GATHER_FWD_CASES, ids=[R.gather_conv_case(r).name for r in R.GATHER_FWD_CASES])
+def test_gather_fwd_case_table_meets_the_conditions(row, dtype):
+    d, ref = R.gather_fwd_reference(row, dtype)
+    assert R.bn_is_telling(d["s"], d["b"])
+    R.fused_conditions(ref, dtype, "fwd " + R.gather_conv_case(row).name)
+    assert bool((d["w"] != 0).any(0).all())
+    assert all(v.shape[1] % 64 == 0 for v in d["srcs"]) and d["srcs"][0].shape[3:] == (row[0][2] // 2, row[0][3] // 2)
+
+
+def test_fwd_accepts_covers_every_live_tile_and_every_refusing_branch():
+    """From the predicate alone: every id in 1 .. NUM_TILE_CFGS other than the retired ones is accepted by at least two rows of different kernel shape or stride
+    class -- tiles 19, 38 and 40, whose launchers admit a single (kernel, stride), by at least two rows of different channels or frame size --, the retired ids
+    by none, and every refusing clause of the restated rule is hit by a row; the clauses no row of the table can reach (the LDS and halo limits need frames wider
+    than any here) by a geometry of their own, on the predicate only."""
+    rows = [c.conv for c in R.FWD_CASES]
+    assert R.NUM_TILE_CFGS == 40 and len(R.LIVE_CFGS) == 36
+    hit = set()
+    for cfg in range(1, R.NUM_TILE_CFGS + 1):
+        took = [c for c in rows if R.fwd_accepts(cfg, c)]
+        for c in rows:
+            hit.update(R.fwd_refusals(cfg, c))
+        if cfg in R.RETIRED_CFGS:
+            assert not took
+            continue
+        classes = {(c.k, c.stride) for c in took}
+        if cfg in R.SINGLE_CLASS_TILES:
+            assert classes == {R.SINGLE_CLASS_TILES[cfg]} and len({(c.cin, c.cout, c.dims) for c in took}) >= 2, (cfg, [c.name for c in took])
+        else:
+            assert len(classes) >= 2, (cfg, [c.name for c in took])
+    by_rows = {"retired", "generic:cin%64", "generic:kpad>1024", "stem:cin!=8", "stem:cout>64", "stem:sw!=1", "pw:geometry", "p8:cin%64", "p8:nk<2", "p8:cout%256",
+               "flat:geometry", "flat:cout>64", "temporal:geometry", "temporal:T>4", "temporal:cout", "patch:geometry", "patch2:geometry", "patch3:cout"}
+    assert by_rows <= hit, sorted(by_rows - hit)
+    # the extras' clauses: on rows of the table
+    stem, e33, pw = (R.case_by_name(rows, n) for n in ("stem_large", "e_3x3_64_64", "e_1x1_64_128"))
+    px = stem.out[0] * stem.out[1] * stem.out[2]
+    for cfg, c, extras, clause in ((9, stem, ("mask",), "stem:extras"), (30, stem, ("y32",), "stem:extras"), (20, stem, (("stats_rows", px + 256),), "stem:stats_rows"),
+                                   (5, stem, (("stats_rows", 128),), "stats_rows<256"), (19, pw, ("stats",), "pw:extras"), (27, e33, ("mask",), "flat:extras"),
+                                   (32, e33, ("ostrided",), "patch:extras"), (38, e33, ("ostrided",), "patch2:extras"), (5, e33, ("gathered",), "gathered:tile"),
+                                   (40, e33, ("gathered",), "patch3:gathered"), (28, R.case_by_name(rows, "t3_T4_256_64"), ("y32",), "temporal:extras"),
+                                   (25, R.case_by_name(rows, "3x3_256_256"), ("stats",), "p8:extras"),
+                                   (32, R.case_by_name(rows, "k333_64_192"), ("gathered",), "gathered:geometry")):
+        assert R.fwd_refusals(cfg, c, extras) == [clause], (cfg, c.name, extras, R.fwd_refusals(cfg, c, extras))
+    for cfg in (9, 20, 29):
+        assert R.fwd_accepts(cfg, stem, ("stats",)) and R.fwd_accepts(cfg, stem, (("stats_rows", px),))
+    for cfg in (5, 32, 38, 40):
+        assert R.fwd_accepts(cfg, e33, ("mask", "y32", "stats"))
+    # the limits no row reaches: a frame 64 wide leaves the flat chunk-major tile's 384-position halo, one 415 wide the flat tile's LDS; a stem with a stride of 7 along h the stem halo's
+    assert R.fwd_refusals(33, R.ConvCase("wide", (1, 1, 4, 64), 64, 64, (1, 3, 3))) == ["patch:halo>384"] and R.fwd_accepts(33, R.ConvCase("w62", (1, 1, 4, 62), 64, 64, (1, 3, 3)))
+    assert R.fwd_refusals(27, R.ConvCase("wider", (1, 1, 2, 415), 64, 64, (1, 3, 3))) == ["flat:lds"] and R.fwd_accepts(27, R.ConvCase("w414", (1, 1, 2, 414), 64, 64, (1, 3, 3)))
+    assert R.fwd_refusals(20, R.ConvCase("stem_s7", (1, 16, 64, 64), 3, 64, (7, 7, 7), (2, 7, 2), pf=(3, 3, 3), pair_w=3)) == ["stem:lds"]
+    # the head / tail split: a 128-wide tile with a sibling splits cout = 136 and 288, not 208 (r = 80) nor anything under a tile without one
+    c136, c288, c208 = (R.case_by_name(rows, n) for n in ("pw_64_136_res", "k333_144_288", "k333_96_208_res"))
+    assert all(R.fwd_is_split(cfg, c136) for cfg in R.NARROW_SIBLING) and not R.fwd_is_split(5, c136) and not R.fwd_is_split(19, c136)
+    assert [cfg for cfg in R.LIVE_CFGS if R.fwd_is_split(cfg, c288) and R.fwd_accepts(cfg, c288)] == [1, 3, 11, 13, 22, 24]       # 6: Kpad > 1024; 18, 23, 35, 36: cin % 64
+    assert not any(R.fwd_is_split(cfg, c208) for cfg in R.LIVE_CFGS)
+    # the ambiguous one, settled from the kernel (conv_igemm_kernel, KS = 2: each wave set multiplies its half of the k16 sub-steps of EVERY K tile, the first included)
+    assert all(R.fwd_accepts(cfg, c136) for cfg in R.SPLIT_K_TILES) and R.FwdGeo(c136).nk == 1
