@@ -619,6 +619,68 @@ int32_t tedspad_mgfn_head(const float *x, int32_t ldx, int32_t M, int32_t C, con
 int32_t tedspad_mgfn_crop_mean(const float *a, float *a_out, const float *b, float *b_out, const int32_t *seg_off, int32_t nvid, int32_t tmax,
                                int32_t ncrops, void *stream);
 
+/* ---- MGFN training (anomaly_detection_mgfn/train.py:79-106, models/mgfn.py:18-86 under model.train()), all fp32 (csrc/mgfn_train.hip) ----
+ * Same layout as the inference entries. No float atomics: every reduction over tokens sums fixed chunks of 128 tokens in order into a
+ * workspace and then the chunks in order, so two runs give the same bits. Data gradients are tedspad_mgfn_gemm products on transposed,
+ * flipped-tap weights; weight gradients are tedspad_mgfn_transpose + tedspad_mgfn_wgrad. */
+/* floats of workspace `ws` that any entry below needs for M tokens and C channels */
+int64_t tedspad_mgfn_train_ws_floats(int32_t M, int32_t C);
+/* Ordered column reductions over the tokens, out = scale * sum_m (...):
+ * mode 0: out0[c] = sum a[m, c];
+ * mode 1: out0 = sum a, out1 = sum a * xh, xh = (x[m, c] - st[2m]) * st[2m + 1] (row statistics of tedspad_mgfn_ln_stats: LayerNorm db, dg);
+ * mode 2: the same with column statistics xh = (x[m, c] - st[c]) * st[C + c] (BatchNorm dbeta, dgamma);
+ * mode 3: out0 = sum (a[m, c] - st[c])^2 (st NULL: mode 0); mode 4: out0 = sum st[m] * a[m, c], out1[c] = sum st[m] (fc dweight, dbias). */
+int32_t tedspad_mgfn_col_reduce(const float *a, int32_t lda, const float *x, int32_t ldx, const float *st, int32_t mode, int32_t M, int32_t C,
+                                float scale, float *ws, float *out0, float *out1, void *stream);
+/* y[m, c] = (x[m, c] - stats[2m]) * stats[2m + 1] * g[c] + b[c]: either LayerNorm, materialised (stats of tedspad_mgfn_ln_stats). */
+int32_t tedspad_mgfn_ln_apply(const float *x, int32_t ldx, const float *stats, const float *g, const float *b, int32_t M, int32_t C, float *y,
+                              int32_t ldy, void *stream);
+/* dx of tedspad_mgfn_ln_apply for dy = d/dy (torch_ln == 0: MGFN's (x - mean) / (std + eps), eps as given to ln_stats; else nn.LayerNorm),
+ * plus add[m, c] when add != NULL (the residual branch's gradient). dg / db: tedspad_mgfn_col_reduce mode 1. */
+int32_t tedspad_mgfn_ln_bwd(const float *dy, int32_t lddy, const float *x, int32_t ldx, const float *stats, const float *g, int32_t torch_ln,
+                            float eps, const float *add, int32_t ldadd, float *dx, int32_t lddx, int32_t M, int32_t C, void *stream);
+/* nn.BatchNorm1d in train mode over all M tokens: stat (2C) = batch mean | 1 / sqrt(biased var + eps); y = (x - mean) invstd gamma + beta;
+ * running_mean / running_var (NULL: none) updated with `momentum`, running_var from the unbiased variance. */
+int32_t tedspad_mgfn_bn_train_fwd(const float *x, int32_t ldx, int32_t M, int32_t C, const float *gamma, const float *beta, float eps,
+                                  float momentum, float *ws, float *stat, float *running_mean, float *running_var, float *y, int32_t ldy,
+                                  void *stream);
+/* its backward: dgamma, dbeta (C) and dx = gamma invstd (dy - dbeta / M - xh dgamma / M) + add (NULL: none). */
+int32_t tedspad_mgfn_bn_train_bwd(const float *dy, int32_t lddy, const float *x, int32_t ldx, const float *stat, const float *gamma, int32_t M,
+                                  int32_t C, float *ws, float *dgamma, float *dbeta, const float *add, int32_t ldadd, float *dx, int32_t lddx,
+                                  void *stream);
+/* Exact-erf GELU over n contiguous floats (n % 4 == 0) and its backward on the kept pre-activation x. */
+int32_t tedspad_mgfn_gelu(const float *x, float *y, int64_t n, void *stream);
+int32_t tedspad_mgfn_gelu_bwd(const float *x, const float *dy, float *dx, int64_t n, void *stream);
+/* out[(t * C + c) * ldo + m] = x[m + t - taps / 2, c], zero outside m's sequence and for M <= m < ldo: the transposed k-tap window matrix.
+ * With ldo % 16 == 0 this image and the transposed dy (N, ldo) are the operands of tedspad_mgfn_wgrad. */
+int32_t tedspad_mgfn_transpose(const float *x, int32_t ldx, const int32_t *bounds, int32_t taps, int32_t M, int32_t C, float *out, int32_t ldo,
+                               void *stream);
+/* Weight gradient dwt (rows, N) = at (rows, ldk) . dyt (N, ldk)^T over the token axis (both from tedspad_mgfn_transpose, ldk % 16 == 0,
+ * N % 64 == 0) on the f32 MFMA: the token axis is cut into slices whose number depends on the shapes only, one wave per 64 x 64 tile and
+ * slice, the slices' partial results go to ws (tedspad_mgfn_wgrad_ws_floats floats; 0: one slice, ws unused) and are added in order. */
+int64_t tedspad_mgfn_wgrad_ws_floats(int32_t ldk, int32_t rows, int32_t N);
+int32_t tedspad_mgfn_wgrad(const float *at, const float *dyt, int32_t ldk, int32_t rows, int32_t N, float *ws, float *dwt, void *stream);
+/* Backward of tedspad_mgfn_attention: o its output, d_o the gradient of o; dqkv rows = dq | dk | dv. lse (M, heads, 2) is scratch (the rows'
+ * log-sum-exp and dO . O). P is recomputed per 32-query / 32-key block. */
+int32_t tedspad_mgfn_attention_bwd(const float *qkv, int32_t ldqkv, const float *o, int32_t ldo, const float *d_o, int32_t lddo,
+                                   const int32_t *seq_off, int32_t nseq, int32_t tmax, int32_t heads, float *lse, float *dqkv, int32_t lddqkv,
+                                   void *stream);
+/* Backward of tedspad_mgfn_relpos: dv[m, c] = sum_t w[c % heads, t] dout[m - t + 2, c]; dw (heads, 5), db (heads). */
+int32_t tedspad_mgfn_relpos_bwd(const float *dout, int32_t lddo, const float *v, int32_t ldv, const int32_t *bounds, int32_t M, int32_t C,
+                                int32_t heads, const float *w, float *ws, float *dv, int32_t lddv, float *dw, float *db, void *stream);
+/* fc -> sigmoid backward: dz[m] = dscore[m] score[m] (1 - score[m]); dh[m, :] += dz[m] fc_w (dh (M, C) in place). The to_logits LayerNorm's
+ * backward is tedspad_mgfn_ln_bwd / col_reduce on dh; fc's gradients are col_reduce mode 4 on h with st = dz. */
+int32_t tedspad_mgfn_head_bwd(const float *score, const float *dscore, const float *fc_w, int32_t M, int32_t C, float *dh, float *dz, void *stream);
+/* MSNSD's training branch and the whole cost, forward and gradient. Videos 0 .. n-1 normal, n .. 2n-1 abnormal, each ncrops x T tokens of C
+ * channels (h, the to_logits output); crop_scores / crop_mags (2n, T) from tedspad_mgfn_crop_mean; masks (2, n, T) = select_idx (abnormal),
+ * select_idx_normal; labels (2n). Out: idx (2n, k) the k largest masked magnitudes, descending, ties to the lowest index; vid_score (2n)
+ * the mean crop-mean score of those; l1 / dl1 (2, ncrops n, k): L1 norms of the selected rows (abnormal, normal; row crop n + video) and
+ * the cost's gradient on them; losses (8) = cost, smooth, sparse, cls, con, con_n, con_a, total; dcs (2n, T), dvid (2n) gradients on the
+ * crop-mean and video scores; dscore (M) and dh (M, C) the gradients on the per-token score and on h (zero off the selected rows). */
+int32_t tedspad_mgfn_msnsd(const float *h, const float *crop_scores, const float *crop_mags, const float *masks, const float *labels, int32_t n,
+                           int32_t ncrops, int32_t T, int32_t C, int32_t k, int32_t *idx, float *vid_score, float *l1, float *losses, float *dl1,
+                           float *dcs, float *dvid, float *dscore, float *dh, void *stream);
+
 /* ---- validation of the action classifier, pictures of the anonymizer (csrc/action_eval.hip) -- all fp32, deterministic, no float atomics ---- */
 
 /* One validation batch behind the ft forward -- train_anonymizer.py:259,272,282-283 / train_anonymized_action.py:156,169,179-180:

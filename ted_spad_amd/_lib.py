@@ -130,6 +130,21 @@ SYMBOLS = {
     "tedspad_mgfn_relpos": (_I32, [_P, _I32, _P, _I32, _I32, _I32, _P, _P, _P, _I32, _P]),
     "tedspad_mgfn_head": (_I32, [_P, _I32, _I32, _I32, _P, _P, _P, C.c_float, C.c_float, _P, _P, _P, _P, _P]),
     "tedspad_mgfn_crop_mean": (_I32, [_P, _P, _P, _P, _P, _I32, _I32, _I32, _P]),
+    "tedspad_mgfn_train_ws_floats": (_I64, [_I32, _I32]),
+    "tedspad_mgfn_col_reduce": (_I32, [_P, _I32, _P, _I32, _P, _I32, _I32, _I32, C.c_float, _P, _P, _P, _P]),
+    "tedspad_mgfn_ln_apply": (_I32, [_P, _I32, _P, _P, _P, _I32, _I32, _P, _I32, _P]),
+    "tedspad_mgfn_ln_bwd": (_I32, [_P, _I32, _P, _I32, _P, _P, _I32, C.c_float, _P, _I32, _P, _I32, _I32, _I32, _P]),
+    "tedspad_mgfn_bn_train_fwd": (_I32, [_P, _I32, _I32, _I32, _P, _P, C.c_float, C.c_float, _P, _P, _P, _P, _P, _I32, _P]),
+    "tedspad_mgfn_bn_train_bwd": (_I32, [_P, _I32, _P, _I32, _P, _P, _I32, _I32, _P, _P, _P, _P, _I32, _P, _I32, _P]),
+    "tedspad_mgfn_gelu": (_I32, [_P, _P, _I64, _P]),
+    "tedspad_mgfn_gelu_bwd": (_I32, [_P, _P, _P, _I64, _P]),
+    "tedspad_mgfn_transpose": (_I32, [_P, _I32, _P, _I32, _I32, _I32, _P, _I32, _P]),
+    "tedspad_mgfn_wgrad_ws_floats": (_I64, [_I32, _I32, _I32]),
+    "tedspad_mgfn_wgrad": (_I32, [_P, _P, _I32, _I32, _I32, _P, _P, _P]),
+    "tedspad_mgfn_attention_bwd": (_I32, [_P, _I32, _P, _I32, _P, _I32, _P, _I32, _I32, _I32, _P, _P, _I32, _P]),
+    "tedspad_mgfn_relpos_bwd": (_I32, [_P, _I32, _P, _I32, _P, _I32, _I32, _I32, _P, _P, _P, _I32, _P, _P, _P]),
+    "tedspad_mgfn_head_bwd": (_I32, [_P, _P, _P, _I32, _I32, _P, _P, _P]),
+    "tedspad_mgfn_msnsd": (_I32, [_P] * 5 + [_I32] * 5 + [_P] * 9 + [_P]),
     "tedspad_softmax_ce_eval": (_I32, [_P] * 7 + [_I32, _I32, _P]),
     "tedspad_vote_accumulate": (_I32, [_P] * 5 + [_I32, _I32, _I32, _P]),
     "tedspad_vote_finalize": (_I32, [_P] * 6 + [_I32, _I32, _P]),
