@@ -59,7 +59,7 @@ __device__ __forceinline__ uint4 pack8_raw(const float (&f)[8]) {
     return make_uint4(w[0], w[1], w[2], w[3]);
 }
 
-// The training forward (always called with `idx`; the inference pools are the kernels below and keep their saturating, NaN-dropping packed maxima).
+// The training forward (always called with `idx`; the inference pools are the kernels below and keep their NaN-dropping packed maxima).
 // max over the window, 8 channels per thread. Padded taps contribute 0 when pad_zero
 // (MaxPool3dSamePadding pads with zeros BEFORE pooling, i3d.py:41-45), else are skipped
 // (nn.MaxPool3d semantics, large_i3d.py:138-139).
@@ -120,9 +120,12 @@ __global__ __launch_bounds__(256) void maxpool_kernel(const PoolKP p) {
 
 // Forward-only variant (no arg-max record): the maximum stays in packed 16-bit form (v_pk_max_f16), ~6x fewer vector
 // instructions per tap than the fp32 compare-and-select above -- the inference pools are then bound by HBM, not by the VALU.
+// The three inference forms share one rule, IEEE maxNum over the taps inside the input (numpy's fmax): a NaN beside a number is dropped, a window of
+// NaNs alone gives NaN, +-inf pass through. So the identity every maximum starts from, and what a skipped tap contributes, is a quiet NaN (`skipw`), not
+// -inf: -inf would turn an all-NaN window into -inf, and only where padding reaches it. With pad_zero the padding contributes 0 as before.
 template <typename T>
-__global__ __launch_bounds__(256) void maxpool_noidx_kernel(const PoolKP p, const uint32_t ninf) {
-    const uint4 lo = make_uint4(ninf, ninf, ninf, ninf), zero = make_uint4(0, 0, 0, 0);
+__global__ __launch_bounds__(256) void maxpool_noidx_kernel(const PoolKP p, const uint32_t skipw) {
+    const uint4 lo = make_uint4(skipw, skipw, skipw, skipw), zero = make_uint4(0, 0, 0, 0);
     for (long idx = (long)blockIdx.x * 256 + threadIdx.x; idx < p.total; idx += (long)gridDim.x * 256) {
         const int c8 = (int)(idx % p.C8);
         long r = idx / p.C8;
@@ -156,7 +159,7 @@ __global__ __launch_bounds__(256) void maxpool_noidx_kernel(const PoolKP p, cons
 // (h0, h0+1) of one 8-channel group: per column it loads the 3(t) x 4(h) inputs once, reduces them to the two column
 // maxima, and an output is the max of three consecutive column maxima kept in registers: 6 loads per output instead of
 // 27, all of them independent 16-byte loads that are contiguous across the lanes (channel-minor).
-// `padv` is what an out-of-range tap contributes: 0 (MaxPool3dSamePadding pads with zeros) or -inf (nn.MaxPool3d).
+// `padv` is what an out-of-range tap contributes: 0 (MaxPool3dSamePadding pads with zeros) or the maximum's identity, a quiet NaN (nn.MaxPool3d).
 template <typename T>
 __global__ __launch_bounds__(256) void maxpool_k3s1_kernel(const uint16_t *x, uint16_t *y, int N, int Tn, int H, int W, int C8, int ldx, int ldy,
                                                            uint32_t padw, int segs, int seglen, long total) {
@@ -595,6 +598,7 @@ extern "C" int32_t tedspad_maxpool_fwd_idx(const tedspad_pool_desc *d, const voi
     p.pad_zero = d->pad_zero;
     p.total = (long)d->n * d->to * d->ho * d->wo * p.C8;
     hipStream_t s = (hipStream_t)stream;
+    const uint32_t skipw = d->dtype == TEDSPAD_F16 ? 0x7E007E00u : 0x7FC07FC0u;          // two quiet NaNs: the identity of maxNum
     if (!idx && d->kt == 3 && d->kh == 3 && d->kw == 3 && d->st == 1 && d->sh == 1 && d->sw == 1 && d->pt == 1 && d->ph == 1 && d->pw == 1 &&
         d->to == d->t && d->ho == d->h && d->wo == d->w) {
         {   // every element fetched once (maxpool_k3s1_lds_kernel) where a frame band fits its per-thread budgets; TEDSPAD_POOL_NO_LDS=1: the column walk (A/B knob)
@@ -611,8 +615,7 @@ extern "C" int32_t tedspad_maxpool_fwd_idx(const tedspad_pool_desc *d, const voi
             const bool fits = rp >= 1 && (hb + rp - 1) / rp <= K3_NO && (hb + 2 + rp - 1) / rp <= K3_NL && lds <= 150 * 1024 && wgs < (1L << 30) &&
                               (long)d->h * d->w * (d->ldx > d->ldy ? d->ldx : d->ldy) < (1L << 31) && (hb >= 4 || hb == d->h);
             if (lds_ok && fits) {
-                const uint32_t ninf2 = d->dtype == TEDSPAD_F16 ? 0xFC00FC00u : 0xFF80FF80u;
-                const uint32_t padw2 = d->pad_zero ? 0u : ninf2;
+                const uint32_t padw2 = d->pad_zero ? 0u : skipw;
                 TS_WITH_T(d->dtype, return launch_lds<maxpool_k3s1_lds_kernel<T>>("tedspad_maxpool_fwd", dim3((unsigned)wgs), dim3(256), (size_t)lds, s, p.x, p.y, d->t, d->h, d->w, p.C8, p.ldx, p.ldy, padw2, g));
             }
         }
@@ -621,14 +624,13 @@ extern "C" int32_t tedspad_maxpool_fwd_idx(const tedspad_pool_desc *d, const voi
         while (rows * segs < 256L * 2048 && (d->w + segs - 1) / segs > 4) ++segs;
         const int seglen = (d->w + segs - 1) / segs;
         const long tot = rows * segs;
-        // a row whose window is entirely padding cannot occur (pad 1 < 3), so with "skip" semantics -inf never survives
-        const uint32_t ninf = d->dtype == TEDSPAD_F16 ? 0xFC00FC00u : 0xFF80FF80u;
-        const uint32_t padw = d->pad_zero ? 0u : ninf;
+        // a window that is entirely padding cannot occur (pad 1 < 3), so with "skip" semantics the identity survives only where every tap is a NaN
+        const uint32_t padw = d->pad_zero ? 0u : skipw;
         TS_LAUNCH_T(d->dtype, maxpool_k3s1_kernel<T>, dim3(grid_for(tot)), dim3(256), 0, s, p.x, p.y, d->n, d->t, d->h, d->w, p.C8, p.ldx, p.ldy, padw, segs, seglen, tot);
         return check_launch("tedspad_maxpool_fwd");
     }
     if (!idx) {
-        TS_LAUNCH_T(d->dtype, maxpool_noidx_kernel<T>, dim3(grid_for(p.total)), dim3(256), 0, s, p, d->dtype == TEDSPAD_F16 ? 0xFC00FC00u : 0xFF80FF80u);
+        TS_LAUNCH_T(d->dtype, maxpool_noidx_kernel<T>, dim3(grid_for(p.total)), dim3(256), 0, s, p, skipw);
         return check_launch("tedspad_maxpool_fwd");
     }
     TS_LAUNCH_T(d->dtype, maxpool_kernel<T>, dim3(grid_for(p.total)), dim3(256), 0, s, p);

@@ -1,7 +1,8 @@
 """float64 references of the memory-bound training kernels (csrc/train_ops.hip, the idx / backward half of csrc/pool_layout.hip, csrc/head.hip, csrc/loss.hip)
 and the two value generators their tests use; then the exact-arithmetic conv references and case tables of tests/test_hip_conv_exact.py and, at the end, the chain
 references, input conditions and case tables of the fused forward kernels (tests/test_hip_fused_exact.py), then the case table of the plain forward conv and the launcher's
-acceptance rule per tile configuration (fwd_accepts; tests/test_hip_conv_fwd_exact.py). A plain helper module: tests/test_kernel_refs.py checks every reference here against float64 torch (autograd) on
+acceptance rule per tile configuration (fwd_accepts; tests/test_hip_conv_fwd_exact.py), then the inference max-pool reference, its launcher's selection restated
+(maxpool_form) and the pool / clip-layout case tables of tests/test_hip_infer_pool.py. A plain helper module: tests/test_kernel_refs.py checks every reference here against float64 torch (autograd) on
 the CPU, the -m gpu op tests (test_hip_train_kernels.py, test_hip_head_ops.py, test_hip_losses.py) compare the kernels with them.
 
 Activations are channels-last: (pixels, C) for the BatchNorm kernels, (n, t, h, w, c) for the pools, (n, h, w, c) for the resizes. Everything returned is a
@@ -1158,3 +1159,238 @@ def gather_fwd_reference(row, dtype, seed=67):
     x = torch.cat([upsample2x_nchw(srcs[0])] + srcs[1:], dim=1)
     d = {"srcs": srcs, "w": small_ints(seed, name + "w", (cout, sum(chans), 1, 3, 3), density=0.5), "s": pow2_scales(cout), "b": nonzero_ints(seed, name + "b", (cout,))}
     return d, chain_ref64(x, [(d["w"], ONE, P011, d["s"], d["b"], None, True)], dtype)
+
+
+# ---- the inference max-pool forms and the clip layouts (csrc/pool_layout.hip; tests/test_hip_infer_pool.py) --------------------------------------------------
+def maxpool_infer_ref(x, k, s, pf, out_dims, pad_zero):
+    """x (n, t, h, w, c) -> (n, to, ho, wo, c), float64 / numpy, from tedspad_pool_desc's semantics: the IEEE maxNum (np.fmax: a NaN beside a number is
+    dropped, NaNs alone give NaN) over the window taps that lie inside the input; with `pad_zero`, an output with at least one tap outside is additionally
+    max'ed with 0. Front padding `pf`; the back padding is whatever `out_dims` implies."""
+    x = x.to(D).numpy()
+    n, T, H, W, c = x.shape
+    To, Ho, Wo = out_dims
+    acc = np.full((n, To, Ho, Wo, c), np.nan)
+    outside = np.zeros((To, Ho, Wo), bool)
+    for dt in range(k[0]):
+        it = np.arange(To) * s[0] - pf[0] + dt
+        for dh in range(k[1]):
+            ih = np.arange(Ho) * s[1] - pf[1] + dh
+            for dw in range(k[2]):
+                iw = np.arange(Wo) * s[2] - pf[2] + dw
+                ok = ((it >= 0) & (it < T))[:, None, None] & ((ih >= 0) & (ih < H))[None, :, None] & ((iw >= 0) & (iw < W))[None, None, :]
+                outside |= ~ok
+                if not ok.any():
+                    continue
+                v = x[:, it.clip(0, T - 1)][:, :, ih.clip(0, H - 1)][:, :, :, iw.clip(0, W - 1)]
+                acc = np.where(ok[None, ..., None], np.fmax(acc, v), acc)
+    if pad_zero:
+        acc = np.where(outside[None, ..., None], np.fmax(acc, 0.0), acc)
+    return torch.from_numpy(acc)
+
+
+def pool_border(thw, k, s, pf, out_dims):
+    """(to, ho, wo) bool: the outputs whose window has at least one tap outside the input."""
+    m = []
+    for size, kk, ss, p, o in zip(thw, k, s, pf, out_dims):
+        lo = np.arange(o) * ss - p
+        m.append((lo < 0) | (lo + kk > size))
+    return torch.from_numpy(m[0][:, None, None] | m[1][None, :, None] | m[2][None, None, :])
+
+
+K3_NL, K3_NO = 10, 8          # pool_layout.hip: input rows / output rows of a frame tile per thread
+
+
+def maxpool_form(d, idx=False, no_lds=False):
+    """The kernel tedspad_maxpool_fwd_idx launches for the descriptor `d` (anything with tedspad_pool_desc's fields), restated clause by clause from the
+    launcher: ('idx',) the fp32 compare-and-select kernel, ('lds', geometry) the frame-band kernel, ('walk', dict(segs, seglen)) the column walk,
+    ('generic',) the packed generic kernel. `no_lds`: a process started with TEDSPAD_POOL_NO_LDS. In the geometry, rp_host is the launcher's rows per
+    pass, rp_last_group what the kernel recomputes for the last (possibly ragged) channel group, live_last_group its number of working threads."""
+    if idx:
+        return ("idx",)
+    C8 = d.c // 8
+    k3 = (d.kt, d.kh, d.kw, d.st, d.sh, d.sw, d.pt, d.ph, d.pw) == (3, 3, 3, 1, 1, 1, 1, 1, 1) and (d.to, d.ho, d.wo) == (d.t, d.h, d.w)
+    if not k3:
+        return ("generic",)
+    CG = C8 if C8 < 8 else 8
+    while CG * 2 <= C8 and d.w * CG * 2 <= 128 and d.h * d.w * CG * 2 <= 2048:
+        CG *= 2
+    rp = 256 // (d.w * CG) if d.w * CG <= 256 else 0
+    hb = d.h
+    while rp and hb > 1 and (-(-hb // rp) > K3_NO or -(-(hb + 2) // rp) > K3_NL):
+        hb -= 1
+    bands, cgroups = -(-d.h // hb), -(-C8 // CG)
+    lds = 2 * (hb + 2) * (d.w + 2) * CG * 16
+    wgs = d.n * bands * cgroups
+    clauses = {"rp": rp >= 1, "rows": rp >= 1 and -(-hb // rp) <= K3_NO and -(-(hb + 2) // rp) <= K3_NL, "lds": lds <= 150 * 1024, "wgs": wgs < 1 << 30,
+               "offsets": d.h * d.w * max(d.ldx, d.ldy) < 1 << 31, "band": hb >= 4 or hb == d.h}
+    if not no_lds and all(clauses.values()):
+        ncg = C8 - (cgroups - 1) * CG
+        rp_last = 256 // (d.w * ncg)
+        return ("lds", dict(CG=CG, HB=hb, bands=bands, cgroups=cgroups, rp_host=rp, rp_last_group=rp_last, live_last_group=rp_last * d.w * ncg,
+                            last_band_rows=d.h - (bands - 1) * hb, lds_bytes=lds))
+    rows = d.n * d.t * ((d.h + 1) // 2) * C8
+    segs = 1
+    while rows * segs < 256 * 2048 and -(-d.w // segs) > 4:
+        segs += 1
+    return ("walk", dict(segs=segs, seglen=-(-d.w // segs), refused=[c for c, v in clauses.items() if not v]))
+
+
+class InferPoolCase:
+    """A row of INFER_POOL_CASES: dims (n, t, h, w), channels, kernel, stride, front padding, back padding (-> the explicit output dims) and the form the row
+    is meant to reach."""
+
+    def __init__(self, name, form, dims, c, k=(3, 3, 3), s=(1, 1, 1), pf=(1, 1, 1), pb=(1, 1, 1)):
+        self.name, self.form, self.dims, self.c, self.k, self.s, self.pf, self.pb = name, form, dims, c, k, s, pf, pb
+        self.n, self.thw = dims[0], tuple(dims[1:])
+        self.out = conv_out_dims(self.thw, k, s, pf, pb)
+
+    def desc(self, ldx=None, ldy=None):
+        """tedspad_pool_desc's geometry fields as a plain object (what maxpool_form reads)."""
+        from types import SimpleNamespace
+        (t, h, w), (kt, kh, kw), (st, sh, sw), (pt, ph, pw), (to, ho, wo) = self.thw, self.k, self.s, self.pf, self.out
+        return SimpleNamespace(n=self.n, t=t, h=h, w=w, c=self.c, ldx=ldx or self.c + 16, ldy=ldy or self.c + 24, kt=kt, kh=kh, kw=kw, st=st, sh=sh, sw=sw,
+                               pt=pt, ph=ph, pw=pw, to=to, ho=ho, wo=wo)
+
+    def geo(self):
+        return maxpool_form(self.desc())[1]
+
+    def x(self):
+        """Signed multiples of 1/64 in [-1.125, 0.125] (81 values, 72 of them negative): exact in f16 and bf16; zero padding beats most border windows'
+        own maximum, and most windows of 4 or more taps still hold a positive value."""
+        u = synth_tensor(71, "ip_" + self.name, tuple(self.dims) + (self.c,)).to(D)
+        return (torch.floor(u * 81).clamp_(0, 80) - 72) / 64
+
+
+_Z, _S2 = (0, 0, 0), (2, 2, 2)
+INFER_POOL_CASES = [
+    # the LDS frame-band form: what each row is there for is asserted by test_kernel_refs.py from maxpool_form alone
+    InferPoolCase("lds_cg32_ragged", "lds", (2, 2, 3, 4), 320),              # CG doubled twice (8 -> 32); the last group has 8 of 32: rp 2 -> 8
+    InferPoolCase("lds_cg64_near_lds_bound", "lds", (2, 3, 16, 2), 512),     # CG doubled three times; 147456 bytes of LDS, the largest the solver can ask for and get
+    InferPoolCase("lds_c8_w40", "lds", (2, 3, 5, 40), 8),                    # C8 = 1 with W > 32: CG = 1, rp 6
+    InferPoolCase("lds_c24_w9", "lds", (2, 2, 7, 9), 24),                    # C8 = 3: CG = 3
+    InferPoolCase("lds_banded_28_t4", "lds", (2, 4, 28, 28), 200),           # rp 1, four bands, the last of 4 rows; last group 1 of 8: rp 9, 252 live threads; T = 4
+    InferPoolCase("lds_banded_odd_t3", "lds", (2, 3, 19, 23), 72),           # rp 1, three bands, the last of 3 rows; last group rp 11, 253 live; T = 3
+    InferPoolCase("lds_banded_w9_t2", "lds", (2, 2, 30, 9), 72),             # rp 3, HB 24, two bands; last group 1 of 8: rp 28; T = 2
+    InferPoolCase("lds_banded_w9_t1", "lds", (3, 1, 30, 9), 64),             # ... T = 1: both temporal neighbours are padding
+    InferPoolCase("lds_w32_t5", "lds", (2, 5, 11, 32), 64),                  # W = 32 with C8 = 8: the last width the form takes; two bands, T = 5
+    InferPoolCase("lds_odd_7x7_c832", "lds", (2, 2, 7, 7), 832),             # InceptionI3d's last modules: CG 16, ragged last group (8 of 16)
+    InferPoolCase("lds_1x1", "lds", (2, 1, 1, 1), 8),                        # every neighbour is padding
+    # the column walk
+    InferPoolCase("walk_w33", "walk", (2, 3, 6, 33), 64),                    # the first width that falls to it; segs 9 x seglen 4 = 36 > 33
+    InferPoolCase("walk_w40_h5", "walk", (2, 2, 5, 40), 64),                 # H odd: the last pair's second row is absent; segs divides W
+    InferPoolCase("walk_h1_w35", "walk", (2, 3, 1, 35), 72),                 # H = 1
+    InferPoolCase("walk_lds_bound_w1", "walk", (2, 3, 16, 1), 1024),         # CG 128: 221184 bytes of LDS refused; seglen 1
+    InferPoolCase("walk_seglen5", "walk", (64, 1, 1, 33), 8192),             # 2^16 rows: segs stops at 8, seglen 5; the eighth run starts past the row. 35 MB, the smallest such
+    # the generic packed kernel: every geometry of test_hip_ops.POOLS that is not 3x3x3 / s1 / p1 ...
+    InferPoolCase("gen_2x3x3_s2", "generic", (2, 4, 15, 14), 64, (2, 3, 3), _S2, _Z, _Z),
+    InferPoolCase("gen_2x1x1_s2", "generic", (2, 4, 9, 9), 256, (2, 1, 1), (2, 1, 1), _Z, _Z),
+    InferPoolCase("gen_1x3x3_s2_same", "generic", (2, 3, 14, 14), 64, (1, 3, 3), (1, 2, 2), _Z, (0, 1, 1)),
+    InferPoolCase("gen_3x3x3_s2_same", "generic", (2, 8, 14, 14), 32, (3, 3, 3), _S2, _Z, (1, 1, 1)),
+    InferPoolCase("gen_2x2x2_s2_odd", "generic", (2, 4, 7, 7), 64, (2, 2, 2), _S2, _Z, (0, 1, 1)),
+    InferPoolCase("gen_1x2x2_s2", "generic", (3, 1, 14, 14), 128, (1, 2, 2), (1, 2, 2), _Z, _Z),
+    # ... and one that looks like the fast path but pads two frames at the back instead of one on each side
+    InferPoolCase("gen_3x3x3_s1_pt0", "generic", (2, 4, 9, 10), 24, (3, 3, 3), (1, 1, 1), (0, 1, 1), (2, 1, 1)),
+]
+INFER_POOL_SPECIAL = ("lds_banded_odd_t3", "walk_w33", "gen_3x3x3_s1_pt0", "gen_1x3x3_s2_same")       # the rows that also run with non-finite inputs
+
+
+def special_values(x):
+    """x (n, t, h, w, c >= 16) with non-finite values planted: channels 0-1 NaN in the first and the last corner block (windows of NaNs alone that padding reaches), 2-3 NaN in an
+    interior block (... that no padding reaches), 4-5 / 6-7 the same with -inf, +inf at two points of channel 8, and single NaNs among the numbers of
+    channels 9 and up."""
+    x = x.clone()
+    assert x.shape[4] >= 16 and x.shape[1] >= 3
+    nan, inf = float("nan"), float("inf")
+    H, W = x.shape[2], x.shape[3]
+    x[:, 0:3, 0:2, 0:4, 0:2] = nan
+    x[:, 0:3, H - 2:, W - 4:, 0:2] = nan
+    x[:, 0:3, 1:6, 5:10, 2:4] = nan
+    x[:, 0:3, 0:2, 0:4, 4:6] = -inf
+    x[:, 0:3, H - 2:, W - 4:, 4:6] = -inf
+    x[:, 0:3, 1:6, 5:10, 6:8] = -inf
+    x[:, 1, 0, 0, 8] = inf
+    x[:, 1, x.shape[2] // 2, x.shape[3] // 2, 8] = inf
+    hole = synth_tensor(72, "ip_hole", tuple(x.shape[:4]) + (x.shape[4] - 9,)) < 0.15
+    x[..., 9:][hole] = nan
+    return x
+
+
+def clip_layout_refusals(c, w, cpad, strides, ptr_mod16):
+    """The clauses of tedspad_clip_to_channels_last's dispatch that keep a clip off the W-contiguous fast path; strides (sn, sc, st, sh, sw) in elements."""
+    sn, sc, st, sh, sw = strides
+    out = []
+    if sw != 1:
+        out.append("sw")
+    if w % 8 != 0:
+        out.append("w8")
+    if c > 4:
+        out.append("c")
+    if ptr_mod16 != 0:
+        out.append("ptr")
+    if sn % 4 or sc % 4 or st % 4 or sh % 4:
+        out.append("stride")
+    return out
+
+
+def clip_layout_form(c, w, cpad, strides, ptr_mod16):
+    return "generic" if clip_layout_refusals(c, w, cpad, strides, ptr_mod16) else "w8"
+
+
+def clip_layout_ref(x, cpad):
+    """(n, c, t, h, w) -> (n, t, h, w, cpad) float64 with channels [c, cpad) zero (cpad 4: two pixels per 16 bytes, the same memory order)."""
+    n, c, t, h, w = x.shape
+    y = torch.zeros((n, t, h, w, cpad), dtype=D)
+    y[..., :c] = x.to(D).permute(0, 2, 3, 4, 1)
+    return y
+
+
+class LayoutCase:
+    """A view (n, c, t, h, w) of a larger contiguous fp32 clip `big`: per dimension (start, size), W optionally with a step, or of a clip stored with H and W
+    swapped (`hw_swapped`: the innermost stride is then H's). The strides and the pointer's offset follow from `big` alone."""
+
+    def __init__(self, name, form, cpad, big, n, c, t, h, w, wstep=1, hw_swapped=False):
+        self.name, self.form, self.cpad, self.big, self.sl, self.wstep, self.hw_swapped = name, form, cpad, big, (n, c, t, h, w), wstep, hw_swapped
+
+    def view(self, big):
+        """`big`: a contiguous tensor of shape self.big (H and W exchanged if hw_swapped)."""
+        if self.hw_swapped:
+            big = big.permute(0, 1, 2, 4, 3)
+        (n0, n), (c0, c), (t0, t), (h0, h), (w0, w) = self.sl
+        return big[n0:n0 + n, c0:c0 + c, t0:t0 + t, h0:h0 + h, w0:w0 + w * self.wstep:self.wstep]
+
+    def storage(self):
+        N, C, T, H, W = self.big
+        return (N, C, T, W, H) if self.hw_swapped else self.big
+
+    def geometry(self):
+        """(c, w, strides, pointer offset in bytes mod 16 from a 16-byte aligned allocation): the arguments of clip_layout_form."""
+        v = self.view(torch.empty(self.storage(), dtype=torch.float32))
+        return v.shape[1], v.shape[4], tuple(v.stride()), (v.storage_offset() * 4) % 16
+
+    def refusals(self):
+        c, w, st, pm = self.geometry()
+        return clip_layout_refusals(c, w, self.cpad, st, pm)
+
+
+def _all(n):
+    return (0, n)
+
+
+LAYOUT_CASES = (
+    # the fast path: T-slices and H / W crops of a larger clip (every stride a multiple of 4, the crop starting on a 16-byte boundary), w = 8 and 72
+    [LayoutCase("w8_c%d_cpad%d" % (c, cpad), "w8", cpad, (3, 4, 6, 12, 80), (1, 2), (0, c), (1, 4), (3, 7), (4, 72)) for cpad in (4, 8) for c in (1, 2, 3, 4)] +
+    [LayoutCase("w8_w8_cpad%d" % cpad, "w8", cpad, (2, 3, 3, 5, 16), _all(2), _all(3), (1, 2), (1, 3), (8, 8)) for cpad in (4, 8)] +
+    [LayoutCase("w8_whole_cpad%d" % cpad, "w8", cpad, (2, 3, 2, 5, 24), _all(2), _all(3), _all(2), _all(5), _all(24)) for cpad in (4, 8)] +
+    # each refusing clause alone
+    [LayoutCase("gen_sw2_cpad%d" % cpad, "generic", cpad, (2, 3, 2, 4, 16), _all(2), _all(3), _all(2), _all(4), (0, 8), wstep=2) for cpad in (4, 8)] +
+    [LayoutCase("gen_w6_cpad4", "generic", 4, (2, 3, 2, 4, 8), _all(2), _all(3), _all(2), _all(4), (0, 6)),
+     LayoutCase("gen_w7_cpad8", "generic", 8, (2, 3, 2, 4, 8), _all(2), _all(3), _all(2), _all(4), (0, 7)),
+     LayoutCase("gen_ptr_cpad4", "generic", 4, (2, 3, 2, 4, 12), _all(2), _all(3), _all(2), _all(4), (1, 8)),
+     LayoutCase("gen_ptr_cpad8", "generic", 8, (2, 3, 2, 4, 12), _all(2), _all(3), _all(2), _all(4), (3, 8)),
+     LayoutCase("gen_stride_cpad4", "generic", 4, (2, 3, 2, 4, 10), _all(2), _all(3), _all(2), _all(4), (0, 8)),
+     LayoutCase("gen_stride_cpad8", "generic", 8, (2, 3, 3, 5, 10), _all(2), _all(3), (1, 2), (1, 3), (0, 8)),
+     LayoutCase("gen_c5_cpad8", "generic", 8, (2, 5, 2, 4, 8), _all(2), _all(5), _all(2), _all(4), _all(8)),
+     LayoutCase("gen_c8_cpad8", "generic", 8, (2, 8, 2, 4, 8), _all(2), _all(8), _all(2), _all(4), _all(8))] +
+    # the generic kernel on the remaining channel counts, odd sizes and a clip stored with H and W exchanged
+    [LayoutCase("gen_c%d_cpad%d" % (c, cpad), "generic", cpad, (2, 4, 3, 7, 10), (0, 2), (0, c), (1, 2), (2, 5), (1, 6)) for cpad in (4, 8) for c in (1, 2, 3, 4)] +
+    [LayoutCase("gen_hw_swapped_cpad%d" % cpad, "generic", cpad, (2, 3, 4, 6, 8), _all(2), _all(3), _all(4), _all(6), _all(8), hw_swapped=True) for cpad in (4, 8)])

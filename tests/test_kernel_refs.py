@@ -462,3 +462,123 @@ def test_fwd_accepts_covers_every_live_tile_and_every_refusing_branch():
     assert not any(R.fwd_is_split(cfg, c208) for cfg in R.LIVE_CFGS)
     # the ambiguous one, settled from the kernel (conv_igemm_kernel, KS = 2: each wave set multiplies its half of the k16 sub-steps of EVERY K tile, the first included)
     assert all(R.fwd_accepts(cfg, c136) for cfg in R.SPLIT_K_TILES) and R.FwdGeo(c136).nk == 1
+
+
+# ---- the inference max-pool forms and the clip layouts -------------------------------------------------------------------------------------------------------
+IP_IDS = [c.name for c in R.INFER_POOL_CASES]
+_ip_refs = {}
+
+
+def ip_refs(case):
+    if case.name not in _ip_refs:
+        x = case.x()
+        _ip_refs[case.name] = (x, R.maxpool_infer_ref(x, case.k, case.s, case.pf, case.out, False), R.maxpool_infer_ref(x, case.k, case.s, case.pf, case.out, True))
+    return _ip_refs[case.name]
+
+
+@pytest.mark.parametrize("case", R.INFER_POOL_CASES, ids=IP_IDS)
+def test_infer_pool_ref_vs_torch_and_the_input_conditions(case):
+    x, skip, zero = ip_refs(case)
+    pad = [v for f, b in zip(reversed(case.pf), reversed(case.pb)) for v in (f, b)]          # F.pad: last dimension first
+    for ref, fill in ((skip, float("-inf")), (zero, 0.0)):
+        want = F.max_pool3d(F.pad(x.permute(0, 4, 1, 2, 3), pad, value=fill), case.k, case.s).permute(0, 2, 3, 4, 1)
+        assert tuple(want.shape[1:4]) == case.out and torch.equal(ref, want)
+    assert float(x.min()) >= -1.125 and float(x.max()) <= 0.125 and torch.equal(x * 64, torch.round(x * 64))
+    assert torch.equal(x.to(torch.float16).to(D), x) and torch.equal(x.to(torch.bfloat16).to(D), x)
+    assert x.numel() < 4096 or 0.85 < float((x < 0).double().mean()) < 0.93          # 72 of the 81 values
+    border = R.pool_border(case.thw, case.k, case.s, case.pf, case.out)
+    assert torch.equal(skip[:, ~border], zero[:, ~border]), "zero padding changed an interior output"
+    if int(border.sum()) * case.n * case.c >= 100:
+        differ = float((skip[:, border] != zero[:, border]).double().mean())
+        positive = float((skip > 0).double().mean())
+        assert differ >= 0.10 and positive >= 0.25, (differ, positive)
+
+
+def test_infer_pool_table_reaches_every_form_and_solver_branch():
+    forms = {c.name: R.maxpool_form(c.desc()) for c in R.INFER_POOL_CASES}
+    for c in R.INFER_POOL_CASES:
+        assert forms[c.name][0] == c.form, (c.name, forms[c.name])
+        assert R.maxpool_form(c.desc(), idx=True) == ("idx",)
+        assert R.maxpool_form(c.desc(), no_lds=True)[0] == ("generic" if c.form == "generic" else "walk")
+        assert c.n >= 2 and c.n * c.thw[0] * c.thw[1] * c.thw[2] * c.c * 2 < 64 << 20
+    lds = [(c, forms[c.name][1]) for c in R.INFER_POOL_CASES if c.form == "lds"]
+    C8 = lambda c: c.c // 8
+    assert any(g["CG"] >= 32 for _, g in lds)                                                                  # (a) CG doubled at least twice
+    assert any(g["CG"] < 8 and g["CG"] == C8(c) for c, g in lds) and any(C8(c) == 1 and c.thw[2] > 32 for c, g in lds)         # (b)
+    assert any(g["rp_host"] == 1 and g["bands"] >= 3 and g["last_band_rows"] < g["HB"] for _, g in lds)       # (c)
+    assert any(g["rp_host"] >= 2 and g["bands"] >= 2 for _, g in lds)                                          # (d)
+    d = [g for c, g in lds if c.thw[1:] == (30, 9)]
+    assert d and all(g["HB"] == 24 for g in d)
+    ragged = [g for c, g in lds if C8(c) % g["CG"] and g["rp_last_group"] != g["rp_host"]]
+    assert len(ragged) >= 3 and any(g["live_last_group"] < 256 for g in ragged) and any(g["live_last_group"] == 256 for g in ragged)          # (e)
+    assert any(c.thw[2] == 32 and C8(c) >= 8 for c, _ in lds)                                                  # (f)
+    assert any(c.thw[2] == 33 and C8(c) >= 8 and c.form == "walk" for c in R.INFER_POOL_CASES)                # (g)
+    assert {c.thw[0] for c, g in lds if g["bands"] >= 2} >= {1, 2, 3, 4}                                       # (h)
+    assert max(g["lds_bytes"] for _, g in lds) == 147456          # the largest request the solver can make and be granted (see below)
+    walk = [(c, forms[c.name][1]) for c in R.INFER_POOL_CASES if c.form == "walk"]
+    assert len({g["seglen"] for _, g in walk}) >= 3 and any(g["seglen"] > 4 and g["segs"] * g["seglen"] - c.thw[2] >= g["seglen"] for c, g in walk)      # ... a run that starts past the row
+    assert any(c.thw[1] % 2 == 1 and c.thw[1] > 1 for c, _ in walk) and any(c.thw[1] == 1 for c, _ in walk)
+    assert any(c.thw[2] % g["segs"] for c, g in walk) and any(c.thw[2] % g["segs"] == 0 for c, g in walk)
+    assert any(g["refused"] == ["lds"] for _, g in walk) and any("rp" in g["refused"] for _, g in walk)
+    assert len({g["seglen"] for c in R.INFER_POOL_CASES if c.form == "lds" for g in [R.maxpool_form(c.desc(), no_lds=True)[1]]}) >= 3          # the child process's walk
+    gen = {(c.k, c.s, c.pf, c.pb) for c in R.INFER_POOL_CASES if c.form == "generic"}
+    assert {((2, 3, 3), (2, 2, 2), (0, 0, 0), (0, 0, 0)), ((2, 1, 1), (2, 1, 1), (0, 0, 0), (0, 0, 0)), ((1, 3, 3), (1, 2, 2), (0, 0, 0), (0, 1, 1)),
+            ((3, 3, 3), (2, 2, 2), (0, 0, 0), (1, 1, 1)), ((2, 2, 2), (2, 2, 2), (0, 0, 0), (0, 1, 1)), ((1, 2, 2), (1, 2, 2), (0, 0, 0), (0, 0, 0))} <= gen
+    assert any(c.k == (3, 3, 3) and c.s == (1, 1, 1) and c.pf[0] == 0 and c.out == c.thw for c in R.INFER_POOL_CASES if c.form == "generic")
+
+
+def test_infer_pool_solver_clauses_no_shape_can_refuse():
+    """Of the LDS form's `fits` test, over every frame up to 64 x 300 and every channel count: the row budgets and `hb >= 4 || hb == h` never refuse once
+    rp >= 1 (the shrink loop ends at hb = min(h, 8 rp) >= 8 or h), and the 150 KB bound refuses only frames of width 1 with CG = 128 (16 rows, 1024 channels
+    and up), which the table has. A seglen above 4 needs rows * segs >= 2^19 at more than 4 columns per run: 2^24 elements or more (H = 1; the table's one such row)."""
+    from types import SimpleNamespace
+    refused = set()
+    for h in range(1, 65):
+        for w in range(1, 301):
+            for C8 in (1, 2, 3, 5, 8, 9, 16, 17, 32, 64, 128, 129, 256):
+                d = SimpleNamespace(n=2, t=2, h=h, w=w, c=8 * C8, ldx=8 * C8, ldy=8 * C8, kt=3, kh=3, kw=3, st=1, sh=1, sw=1, pt=1, ph=1, pw=1, to=2, ho=h, wo=w)
+                f = R.maxpool_form(d)
+                if f[0] == "walk":
+                    r = f[1]["refused"]
+                    refused.add((("rp",), 0) if "rp" in r else (tuple(r), w))          # without a row per pass (W * CG > 256) the other clauses say nothing
+                    assert f[1]["seglen"] <= 4 or d.n * d.t * h * w * d.c >= 1 << 24
+    assert refused == {(("rp",), 0), (("lds",), 1)}, refused
+
+
+@pytest.mark.parametrize("name", R.INFER_POOL_SPECIAL)
+def test_infer_pool_special_values_hold_every_class(name):
+    case = R.case_by_name(R.INFER_POOL_CASES, name)
+    x = R.special_values(case.x())
+    skip, zero = (R.maxpool_infer_ref(x, case.k, case.s, case.pf, case.out, pz) for pz in (False, True))
+    has_nan = R.maxpool_infer_ref(torch.isnan(x).to(D), case.k, case.s, case.pf, case.out, False) > 0
+    nan_s, nan_z = int(torch.isnan(skip).sum()), int(torch.isnan(zero).sum())
+    assert nan_s > nan_z >= 1                                   # windows of NaNs alone: NaN, but 0 where zero padding reaches them
+    assert bool((zero[torch.isnan(skip) & ~torch.isnan(zero)] == 0).all())
+    assert int((has_nan & torch.isfinite(skip)).sum()) >= 100        # NaNs beside numbers are dropped
+    ninf_s, ninf_z = int((skip == float("-inf")).sum()), int((zero == float("-inf")).sum())
+    assert ninf_s > ninf_z >= 1 and int((skip == float("inf")).sum()) >= 2 and torch.equal(skip == float("inf"), zero == float("inf"))
+
+
+def test_layout_table_and_reference():
+    rows = {c.name: c for c in R.LAYOUT_CASES}
+    assert len(rows) == len(R.LAYOUT_CASES)
+    for c in R.LAYOUT_CASES:
+        ch, w, strides, pm = c.geometry()
+        assert R.clip_layout_form(ch, w, c.cpad, strides, pm) == c.form, (c.name, c.refusals())
+        assert ch <= c.cpad and (c.cpad == 8 or w % 2 == 0)
+    for cpad in (4, 8):
+        sub = [c for c in R.LAYOUT_CASES if c.cpad == cpad]
+        for form in ("w8", "generic"):
+            assert {c.geometry()[0] for c in sub if c.form == form} >= {1, 2, 3, 4}, (cpad, form)
+        assert {c.geometry()[1] for c in sub if c.form == "w8"} >= {8, 72}
+        assert any(c.geometry()[2] != torch.empty(c.sl[0][1], c.sl[1][1], c.sl[2][1], c.sl[3][1], c.sl[4][1]).stride() for c in sub if c.form == "w8")
+    assert {c.geometry()[0] for c in R.LAYOUT_CASES if c.cpad == 8 and c.form == "generic"} >= {5, 8}
+    alone = {tuple(c.refusals()) for c in R.LAYOUT_CASES}
+    assert {("sw",), ("w8",), ("ptr",), ("stride",), ("c",)} <= alone                  # each refusing clause of the dispatch, by itself
+    x = synth_tensor(73, "lay", (2, 3, 2, 3, 4)).to(D)
+    for cpad in (4, 8):
+        y = R.clip_layout_ref(x, cpad)
+        assert y.shape == (2, 2, 3, 4, cpad) and float(y[..., 3:].abs().max()) == 0.0
+        for ch in range(3):
+            assert torch.equal(y[..., ch], x[:, ch])
+        assert torch.equal(y.reshape(2, 2, 3, 2, 2 * cpad)[..., cpad:cpad + 3], x.permute(0, 2, 3, 4, 1)[:, :, :, 1::2])        # cpad 4: the pair's second pixel
