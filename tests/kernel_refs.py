@@ -2,7 +2,8 @@
 and the two value generators their tests use; then the exact-arithmetic conv references and case tables of tests/test_hip_conv_exact.py and, at the end, the chain
 references, input conditions and case tables of the fused forward kernels (tests/test_hip_fused_exact.py), then the case table of the plain forward conv and the launcher's
 acceptance rule per tile configuration (fwd_accepts; tests/test_hip_conv_fwd_exact.py), then the inference max-pool reference, its launcher's selection restated
-(maxpool_form) and the pool / clip-layout case tables of tests/test_hip_infer_pool.py. A plain helper module: tests/test_kernel_refs.py checks every reference here against float64 torch (autograd) on
+(maxpool_form) and the pool / clip-layout case tables of tests/test_hip_infer_pool.py, and last the weight-image, BatchNorm-fold and gradient-unpack references (numpy) and
+case table of tests/test_hip_pack_exact.py. A plain helper module: tests/test_kernel_refs.py checks every reference here against float64 torch (autograd) on
 the CPU, the -m gpu op tests (test_hip_train_kernels.py, test_hip_head_ops.py, test_hip_losses.py) compare the kernels with them.
 
 Activations are channels-last: (pixels, C) for the BatchNorm kernels, (n, t, h, w, c) for the pools, (n, h, w, c) for the resizes. Everything returned is a
@@ -1394,3 +1395,297 @@ LAYOUT_CASES = (
     # the generic kernel on the remaining channel counts, odd sizes and a clip stored with H and W exchanged
     [LayoutCase("gen_c%d_cpad%d" % (c, cpad), "generic", cpad, (2, 4, 3, 7, 10), (0, 2), (0, c), (1, 2), (2, 5), (1, 6)) for cpad in (4, 8) for c in (1, 2, 3, 4)] +
     [LayoutCase("gen_hw_swapped_cpad%d" % cpad, "generic", cpad, (2, 3, 4, 6, 8), _all(2), _all(3), _all(4), _all(6), _all(8), hw_swapped=True) for cpad in (4, 8)])
+
+
+# ---- the weight images, folded BatchNorm vectors and gradient unpack of csrc/pack.hip (tests/test_hip_pack_exact.py) ---------------------------------------
+# Restated from the layout comment at the top of pack.hip and the header's documentation, in numpy. The 16-bit roundings are written out here (numpy's own
+# float16 for f16, integer arithmetic on the fp32 bits for bf16) and test_kernel_refs.py holds them against torch's conversions.
+F16_MAX = 65504.0
+PK_FLOATS = 64 * (8 * 27 + 1)              # pack.hip: the largest LDS tile, in floats
+PK_FWD_FLOATS = 4096                       # pack.hip: a forward tile holds as many whole rows as fit this
+PK_MAX_BLOCKS = 256                        # pack.hip: workgroups per job of a multi-job launch
+SENTINEL16 = 0x7E7E                        # what destinations and guards hold before a pack
+
+
+def _np32(t):
+    if t is None:
+        return None
+    return np.ascontiguousarray(t.detach().cpu().numpy() if isinstance(t, torch.Tensor) else t, dtype=np.float32)
+
+
+def round16_bits(v32, dtype):
+    """fp32 numpy array -> the int16 bit patterns of the 16-bit type: ONE round-to-nearest-even; f16 clamped to +-65504 first, bf16 not clamped. No NaN / Inf."""
+    v32 = np.ascontiguousarray(v32, dtype=np.float32)
+    assert bool(np.isfinite(v32).all())
+    if dtype == "f16":
+        return np.clip(v32, np.float32(-F16_MAX), np.float32(F16_MAX)).astype(np.float16).view(np.int16)
+    b = v32.view(np.uint32).astype(np.uint64)
+    return ((b + 0x7FFF + ((b >> 16) & 1)) >> 16).astype(np.uint16).view(np.int16)
+
+
+def kernel_form(w, cink, kwk, pair_shift):
+    """wk of pack.hip's layout comment: (co, cink, kt, kh, kwk) -- channels zero-padded, or the pixel-pair form wk(n, j*4 + c, dt, dh, d) = w(n, c, dt, dh, 2d + j - shift)."""
+    co, ci, kt, kh, kw = w.shape
+    wk = np.zeros((co, cink, kt, kh, kwk), dtype=w.dtype)
+    if pair_shift < 0:
+        assert kwk == kw and cink >= ci
+        wk[:, :ci] = w
+        return wk
+    assert ci <= 4 and cink == 8
+    for d in range(kwk):
+        for j in range(2):
+            k = 2 * d + j - pair_shift
+            if 0 <= k < kw:
+                wk[:, j * 4:j * 4 + ci, :, :, d] = w[..., k]
+    return wk
+
+
+def pack_image_ref(w, scale, *, cink, kwk, pair_shift, mode, rows, rows_pad, kpad, geo, dtype):
+    """The (rows_pad, kpad) int16 bit image tedspad_pack_conv_weights / a tedspad_pack_job writes for the fp32 parameter w (co, ci, kt, kh, kw):
+    w * scale[co] is ONE fp32 multiply, then one rounding to the 16-bit type (round16_bits); everything outside [rows) x [K) is +0.
+    mode 0: out[n][((dt*KH + dh)*KWk + dw)*CINk + c]; mode 1: out[c][((et*Eh + eh)*Ew + ew)*CO8 + n] with tap = c. + s.*(E. - 1 - e.), geo = (Et,Eh,Ew, ct,ch,cw, st,sh,sw)."""
+    w, scale = _np32(w), _np32(scale)
+    co, ci, kt, kh, kw = w.shape
+    p = w if scale is None else w * scale.reshape(co, 1, 1, 1, 1)                  # float32 * float32 -> float32
+    assert p.dtype == np.float32
+    wk = kernel_form(p, cink, kwk, pair_shift)
+    img = np.zeros((rows_pad, kpad), dtype=np.float32)
+    if mode == 0:
+        K = kt * kh * kwk * cink
+        assert K <= kpad and rows <= co and rows <= rows_pad
+        img[:rows, :K] = wk.transpose(0, 2, 3, 4, 1).reshape(co, K)[:rows]
+    else:
+        Et, Eh, Ew, ct, ch, cw, st, sh, sw = geo
+        co8 = (co + 7) // 8 * 8
+        assert Et * Eh * Ew * co8 <= kpad and rows <= cink and rows <= rows_pad
+        for et in range(Et):
+            for eh in range(Eh):
+                for ew in range(Ew):
+                    dt, dh, dw = ct + st * (Et - 1 - et), ch + sh * (Eh - 1 - eh), cw + sw * (Ew - 1 - ew)
+                    k0 = ((et * Eh + eh) * Ew + ew) * co8
+                    img[:rows, k0:k0 + co] = wk[:, :rows, dt, dh, dw].T
+    return round16_bits(img, dtype)
+
+
+class PkPlan:
+    def __init__(self, tiled, per_tile, tiles):
+        self.tiled, self.per_tile, self.tiles = tiled, per_tile, tiles
+
+    def blocks(self, rows_pad, kpad):
+        """Workgroups the job gets in a multi-job launch."""
+        g = self.tiles if self.tiled else (rows_pad * (kpad // 8) + 1023) // 1024
+        return max(1, min(PK_MAX_BLOCKS, g))
+
+
+def pk_plan_ref(mode, pair_shift, kw, kwk, ci, taps, rows_pad, co8):
+    """pk_plan of pack.hip restated: does a job of tedspad_pack_multi go through LDS tiles, how many rows (mode 0) / input channels (mode 1) a tile holds and how
+    many tiles it has. Not tiled (pack_body, the gather): pixel-pair forms, forward rows longer than the largest tile, data gradients with more than 27 taps.
+    `taps` = kt * kh * kw of the whole kernel, in both modes."""
+    if pair_shift >= 0 or kwk != kw:
+        return PkPlan(False, 0, 0)
+    if mode == 0:
+        run = ci * taps
+        if run > PK_FLOATS:
+            return PkPlan(False, 0, 0)
+        R = max(1, min(64, PK_FWD_FLOATS // run))
+        return PkPlan(True, R, (rows_pad + R - 1) // R)
+    if taps > 27:
+        return PkPlan(False, 0, 0)
+    C = 32 if taps == 1 else 16 if taps <= 3 else 8
+    return PkPlan(True, C, ((rows_pad + C - 1) // C) * ((co8 + 63) // 64))
+
+
+def fold_ref64(gamma, beta, mean, var, eps, conv_bias=None, n=None):
+    """Eval-mode BatchNorm folded to (scale, shift) in numpy float64: scale = gamma / sqrt(var + eps), shift = beta - mean*scale (+ conv_bias*scale).
+    gamma None: no BatchNorm -- scale = 1 and shift = conv_bias, or 0 (then `n` gives the length)."""
+    f = lambda t: None if t is None else (t.detach().cpu().numpy() if isinstance(t, torch.Tensor) else np.asarray(t)).astype(np.float64)
+    gamma, beta, mean, var, conv_bias = f(gamma), f(beta), f(mean), f(var), f(conv_bias)
+    if gamma is None:
+        n = len(conv_bias) if conv_bias is not None else n
+        return np.ones(n), (conv_bias if conv_bias is not None else np.zeros(n))
+    scale = gamma / np.sqrt(var + np.float64(eps))
+    shift = beta - mean * scale
+    if conv_bias is not None:
+        shift = shift + conv_bias * scale
+    return scale, shift
+
+
+def ulp32(x64):
+    """The fp32 spacing at |x| (float64 in, float64 out): 2^(e - 23) for 2^e <= |x| < 2^(e+1), never below the subnormal step 2^-149."""
+    a = np.abs(np.asarray(x64, dtype=np.float64))
+    _, e = np.frexp(a)                                                      # |x| = m * 2^e, m in [0.5, 1)
+    return np.ldexp(1.0, np.where(a == 0, -149, np.maximum(e - 24, -149)))
+
+
+def wgrad_unpack_ref(dw, co, ci, k, cink, kpad, row_scale=None, grad0=None):
+    """grad[n, c, tap] = (grad0 or 0) + dw[n, tap*cink + c] * row_scale[n], float64, shaped (co, ci, kt, kh, kw); dw: the packed [>= co][kpad] accumulator."""
+    dw = np.asarray(dw, dtype=np.float64)
+    taps = k[0] * k[1] * k[2]
+    assert dw.shape[1] == kpad and taps * cink <= kpad and ci <= cink
+    g = dw[:co, :taps * cink].reshape(co, taps, cink)[:, :, :ci].transpose(0, 2, 1)
+    if row_scale is not None:
+        g = g * np.asarray(row_scale, dtype=np.float64)[:co].reshape(co, 1, 1)
+    if grad0 is not None:
+        g = g + np.asarray(grad0, dtype=np.float64).reshape(co, ci, taps)
+    return g.reshape(co, ci, *k)
+
+
+# values planted into every case's weights (fp32): an f16 tie above an even and above an odd mantissa, the same for bf16, f16 subnormals (one inexact, one a tie, one
+# half the smallest subnormal), -0.0, values above 65504 (65520 is the tie between 65504 and what would be +inf) and one just below that tie
+PACK_PLANTS = np.array([1 + 2.0 ** -11, 1 + 3 * 2.0 ** -11, -(1 + 3 * 2.0 ** -11), 1 + 2.0 ** -8, 1 + 3 * 2.0 ** -8, -(1 + 2.0 ** -8), 3.3e-6, 2.5 * 2.0 ** -24,
+                        2.0 ** -25, -0.0, 70000.0, -1.0e6, 65520.0, 65519.99], dtype=np.float32)
+
+
+def pack_weights(shape, seed):
+    """(w, scale) fp32 numpy: w random in (-1, 1) with PACK_PLANTS written into output channels 0, 4, 8, ... (co >= 8); scale in +-[0.5, 1.5) with every fourth
+    entry exactly 1, so the planted values reach the rounding unchanged with and without the scale."""
+    co = shape[0]
+    per = int(np.prod(shape[1:]))
+    w = synth_tensor(seed, "pack_w", shape, -1, 1).numpy().astype(np.float32).reshape(co, per)
+    pos = (synth_tensor(seed, "pack_pos", (len(PACK_PLANTS),)).numpy() * per).astype(np.int64).clip(0, per - 1)
+    rows4 = (co + 3) // 4
+    for i, v in enumerate(PACK_PLANTS):
+        r, c = 4 * (i % rows4), int(pos[i])
+        while any(r == 4 * (j % rows4) and c == int(pos[j]) for j in range(i)):       # two plants drew the same slot
+            c = (c + 1) % per
+        pos[i] = c
+        w[r, c] = v
+    s = synth_tensor(seed, "pack_s", (co,), 0.5, 1.5).numpy().astype(np.float32)
+    s[1::2] *= -1
+    s[::4] = 1.0
+    return w.reshape(shape), s
+
+
+def _once_from_exact(x64, dtype):
+    """float64 -> the 16-bit type in ONE rounding (as int16 bits, f16 clamped): numpy's float64 -> float16 for f16; for bf16 round to odd into fp32 first
+    (fp32 keeps 16 more bits than bf16, so the second rounding then sees exactly which side of a tie the value lies on)."""
+    if dtype == "f16":
+        return np.clip(x64, -F16_MAX, F16_MAX).astype(np.float16).view(np.int16)
+    f = x64.astype(np.float32)
+    inexact = f.astype(np.float64) != x64
+    away = np.abs(f.astype(np.float64)) > np.abs(x64)
+    t = np.where(away, np.nextafter(f, np.float32(0)), f)                   # truncated toward zero
+    t = np.where(inexact, (t.view(np.uint32) | np.uint32(1)).view(np.float32), t)
+    return round16_bits(t, dtype)
+
+
+def rounding_ingredients(w, scale, dtype):
+    """Counts, over the products the pack rounds, of what makes its arithmetic visible: ties over an even / an odd mantissa (normal range of the type), products whose
+    fp32 rounding changes the 16-bit result against rounding the exact product once, f16-subnormal magnitudes, -0.0 and magnitudes above 65504."""
+    w = _np32(w)
+    co = w.shape[0]
+    s = np.ones(co, dtype=np.float32) if scale is None else _np32(scale)
+    p = (w.reshape(co, -1) * s.reshape(co, 1)).reshape(-1)
+    exact = (w.reshape(co, -1).astype(np.float64) * s.reshape(co, 1).astype(np.float64)).reshape(-1)          # 24 x 24 bits: exact in float64
+    b = p.view(np.uint32)
+    a = np.abs(p)
+    drop = 13 if dtype == "f16" else 16
+    normal = (a >= 2.0 ** -14) & (a < F16_MAX) if dtype == "f16" else (a >= 2.0 ** -126)
+    tie = normal & ((b & ((1 << drop) - 1)) == (1 << (drop - 1)))
+    odd = ((b >> drop) & 1) == 1
+    return {"tie_even": int((tie & ~odd).sum()), "tie_odd": int((tie & odd).sum()),
+            "double_rounding": int((round16_bits(p, dtype) != _once_from_exact(exact, dtype)).sum()),
+            "f16_subnormal": int(((a > 0) & (a < 2.0 ** -14)).sum()), "neg_zero": int(((p == 0) & np.signbit(p)).sum()), "above_f16_max": int((a > F16_MAX).sum())}
+
+
+class PackCase:
+    """One convolution of the weight-image tests: the parameter's shape, its stride / front pads, the stem's pair_w, the kernel-form input dims a DgradPlan is built for,
+    and the path each of its images must take in a multi-job launch (checked through pk_plan_ref):
+      fwd / dgrad = (tiled, per_tile, over_cap): LDS tiles or pack_body, rows / channels per tile, more tiles than the 256 workgroups of a job;
+      class_taps: taps of every parity class of the data gradient; last_chunks: 8-channel chunks of the last 64-wide co tile."""
+
+    def __init__(self, name, shape, stride=ONE, pads=(0, 0, 0), pair_w=None, in_dims=(2, 4, 4), fwd=None, dgrad=None, class_taps=(1,), last_chunks=None):
+        self.name, self.shape, self.stride, self.pads, self.pair_w, self.in_dims = name, shape, stride, pads, pair_w, in_dims
+        self.fwd, self.dgrad, self.class_taps, self.last_chunks = fwd, dgrad, tuple(class_taps), last_chunks
+        co, ci, kt, kh, kw = shape
+        self.co8 = (co + 7) // 8 * 8
+        if pair_w is None:
+            self.cink, self.kwk, self.pair_shift = (ci + 7) // 8 * 8, kw, -1
+            self.stride_k, self.pads_k = tuple(stride), tuple(pads)
+        else:                                                                       # engine.PackedConv: the pixel-pair form, stride 1 along W
+            pw2 = (pair_w + 1) // 2
+            self.pair_shift = 2 * pw2 - pair_w
+            self.cink, self.kwk = 8, (kw + self.pair_shift + 1) // 2
+            self.stride_k, self.pads_k = (stride[0], stride[1], 1), (pads[0], pads[1], pw2)
+        self.k_k = (kt, kh, self.kwk)
+        self.out_dims = conv_out_dims(in_dims, self.k_k, self.stride_k, self.pads_k, (self.pads_k[0], self.pads_k[1], self.k_k[2] - 1 - self.pads_k[2]) if pair_w is not None else self.pads_k)
+
+    def classes(self):
+        """geo = (Et,Eh,Ew, ct,ch,cw, st,sh,sw) of every parity class of the data gradient: the taps c, c + s, ... < k of each residue c of (r + front pad) mod s."""
+        out = []
+        for rt in range(self.stride_k[0]):
+            for rh in range(self.stride_k[1]):
+                for rw in range(self.stride_k[2]):
+                    c = [(r + pf) % s for r, pf, s in zip((rt, rh, rw), self.pads_k, self.stride_k)]
+                    E = [len(range(cc, k, s)) for cc, k, s in zip(c, self.k_k, self.stride_k)]
+                    if min(E) > 0:
+                        out.append(tuple(E) + tuple(c) + self.stride_k)
+        return out
+
+    def image_dims(self, mode, geo=None):
+        """(rows, rows_pad, kpad) as tedspad_conv_cout_pad / tedspad_conv_kpad pad them: rows to 128, K to 64."""
+        rows = self.shape[0] if mode == 0 else self.cink
+        K = self.k_k[0] * self.k_k[1] * self.k_k[2] * self.cink if mode == 0 else geo[0] * geo[1] * geo[2] * self.co8
+        return rows, (rows + 127) // 128 * 128, (K + 63) // 64 * 64
+
+    def plan(self, mode, geo=None):
+        co, ci, kt, kh, kw = self.shape
+        return pk_plan_ref(mode, self.pair_shift, kw, self.kwk, ci, kt * kh * kw, self.image_dims(mode, geo)[1], self.co8)
+
+    def pack_args(self, mode, geo=None):
+        """The keyword arguments of pack_image_ref for one image of this case."""
+        rows, rows_pad, kpad = self.image_dims(mode, geo)
+        return dict(cink=self.cink, kwk=self.kwk, pair_shift=self.pair_shift, mode=mode, rows=rows, rows_pad=rows_pad, kpad=kpad, geo=geo)
+
+
+BODY = (False, 0, False)
+PACK_CASES = [
+    PackCase("stem_pairs", (64, 3, 5, 7, 7), (2, 2, 2), (2, 3, 3), pair_w=3, in_dims=(4, 16, 8), fwd=BODY, dgrad=BODY, class_taps=(48, 36, 32, 24)),
+    # forward tile of several rows; ci a multiple of 8 but co not (co8 = 24); data-gradient tiles of 8 channels; the four parity classes of a strided 3 x 3
+    PackCase("rows_per_tile_co20_s2", (20, 40, 1, 3, 3), (1, 2, 2), (0, 1, 1), fwd=(True, 11, False), dgrad=(True, 8, False), class_taps=(1, 2, 2, 4), last_chunks=3),
+    # data-gradient tiles of 16 channels with ci < 16 (and no multiple of 8); co8 = 96: a second co tile with 4 chunks
+    PackCase("dgrad_c16_two_co_tiles", (96, 12, 3, 1, 1), ONE, (1, 0, 0), in_dims=(2, 2, 2), fwd=(True, 64, False), dgrad=(True, 16, False), class_taps=(3,), last_chunks=4),
+    # data-gradient tiles of 32 channels, the last channel tile partly filled (ci = 72), one parity class, a third co tile with one chunk
+    PackCase("dgrad_c32_s2", (136, 72, 1, 1, 1), (1, 2, 2), fwd=(True, 56, False), dgrad=(True, 32, False), class_taps=(1,), last_chunks=1),
+    # a forward row longer than PK_FWD_FLOATS: one row per tile, 384 tiles on 256 workgroups; data gradient 80 x 5 = 400 tiles on 256 workgroups
+    PackCase("long_rows_over_cap", (300, 520, 1, 3, 3), (1, 2, 2), (0, 1, 1), fwd=(True, 1, True), dgrad=(True, 8, True), class_taps=(1, 2, 2, 4), last_chunks=6),
+    # the longest forward row that is still tiled (13 887 floats, ci % 8 != 0), and 8 floats more: pack_body inside the multi-job launch
+    PackCase("longest_tiled_row", (16, 1543, 1, 3, 3), ONE, (0, 1, 1), fwd=(True, 1, False), dgrad=(True, 8, False), class_taps=(9,), last_chunks=2),
+    PackCase("row_too_long", (16, 1544, 1, 3, 3), ONE, (0, 1, 1), fwd=BODY, dgrad=(True, 8, False), class_taps=(9,), last_chunks=2),
+    # plain data gradients with 27 taps (the most that is tiled) and with 49 (pack_body)
+    PackCase("dgrad_27_taps", (8, 8, 3, 3, 3), ONE, (1, 1, 1), fwd=(True, 18, False), dgrad=(True, 8, False), class_taps=(27,), last_chunks=1),
+    PackCase("dgrad_49_taps", (24, 8, 1, 7, 7), ONE, (0, 3, 3), in_dims=(1, 8, 8), fwd=(True, 10, False), dgrad=BODY, class_taps=(49,)),
+    # forward rows per tile capped at 64 with more than 256 tiles; the data gradient has 257 co tiles (the last with 2 chunks)
+    PackCase("rows_capped_over_cap", (16400, 8, 1, 1, 1), fwd=(True, 64, True), dgrad=(True, 32, True), class_taps=(1,), last_chunks=2),
+]
+PACK_BIG = "long_rows_over_cap"            # the job the find_job tables spread 256 workgroups at a time
+FIND_JOB_SIZES = (1, 2, 63, 64, 65, 4095, 4096, 4097)
+FOLD_C = (1, 255, 256, 257, 2048)
+
+
+def find_job_rounds(n):
+    """Rounds of the 64-ary search over a table of n jobs (1 up to 64, 2 up to 4096, ...)."""
+    r = 0
+    while n > 1:
+        n, r = (n + 63) // 64, r + 1
+    return r
+
+
+def fold_inputs(C, seed):
+    """(gamma, beta, mean, var, conv_bias) fp32 numpy: some gamma negative, some var exactly 0."""
+    g = synth_tensor(seed, "fold_g", (C,), -1.5, 1.5).numpy().astype(np.float32)
+    be = synth_tensor(seed, "fold_b", (C,), -0.5, 0.5).numpy().astype(np.float32)
+    m = synth_tensor(seed, "fold_m", (C,), -2.0, 2.0).numpy().astype(np.float32)
+    v = synth_tensor(seed, "fold_v", (C,), 0.0, 3.0).numpy().astype(np.float32)
+    v[::5] = 0.0
+    cb = synth_tensor(seed, "fold_cb", (C,), -1.0, 1.0).numpy().astype(np.float32)
+    return g, be, m, v, cb
+
+
+def fold_shift_bound(ref_shift, beta, mean, scale64, conv_bias=None):
+    """|shift - ref64| allowed: the fp32 rounding of a value within a few double ulps of the reference -- 1/2 ulp32(ref) + 4 * 2^-52 * (|beta| + |mean*scale| + |b*scale|).
+    (The library is built with -ffp-contract=fast: beta - mean*scale may be one FMA or a multiply and an add.)"""
+    mag = np.abs(np.asarray(beta, np.float64)) + np.abs(np.asarray(mean, np.float64) * scale64)
+    if conv_bias is not None:
+        mag = mag + np.abs(np.asarray(conv_bias, np.float64) * scale64)
+    return 0.5 * ulp32(ref_shift) + 4 * 2.0 ** -52 * mag

@@ -8,7 +8,6 @@ import torch
 from ted_spad_amd.synth import synth_tensor
 
 pytestmark = pytest.mark.gpu
-H = torch.float16
 
 # name, (co, ci, kt, kh, kw), stride, pads, pair_w, bias, x dims (t, h, w)
 LAYERS = [
@@ -20,7 +19,7 @@ LAYERS = [
 ]
 
 
-def _layers():
+def _layers(dtype="f16"):
     from ted_spad_amd import train_engine as TE
     from ted_spad_amd.params import BNParams
     out = []
@@ -31,18 +30,19 @@ def _layers():
         with torch.no_grad():
             bn.weight.copy_(synth_tensor(20 + i, "g", (shape[0],), 0.5, 1.5)); bn.bias.copy_(synth_tensor(20 + i, "be", (shape[0],), -0.3, 0.3))
             bn.running_mean.copy_(synth_tensor(20 + i, "m", (shape[0],), -0.2, 0.2)); bn.running_var.copy_(synth_tensor(20 + i, "v", (shape[0],), 0.5, 2.0))
-        out.append((TE.ConvLayer(w, b, stride, pads, pair_w=pair_w), bn, xd))
+        out.append((TE.ConvLayer(w, b, stride, pads, pair_w=pair_w, dtype=dtype), bn, xd))
     return out
 
 
 def _acts(L, xd, n=2):
-    """(x, dy) Acts of the right shapes for layer L."""
+    """(x, dy) Acts of the right shapes for layer L, in its storage type."""
     from ted_spad_amd import engine as E
+    H = E.DTYPES[L.dtype][0]
     co, ci = L.weight.shape[:2]
     k = tuple(L._w5().shape[2:])
     od = tuple(E.conv_out(xd[i], k[i], L.stride[i], L.pads[i], L.pads_back[i]) for i in range(3))
     if L.pair_w is not None:
-        x = E.clip_to_act(synth_tensor(3, "x", (n, ci) + xd, -1, 1).cuda(), cpad=4, dtype="f16")
+        x = E.clip_to_act(synth_tensor(3, "x", (n, ci) + xd, -1, 1).cuda(), cpad=4, dtype=L.dtype)
     else:
         cin = (ci + 7) // 8 * 8
         xb = torch.zeros((n,) + xd + (cin,), dtype=H, device="cuda")
@@ -54,12 +54,13 @@ def _acts(L, xd, n=2):
     return x, E.Act(db, c8)
 
 
-def test_refreshed_images_equal_a_fresh_pack():
+@pytest.mark.parametrize("dtype", ("f16", "bf16"))
+def test_refreshed_images_equal_a_fresh_pack(dtype):
     """Every image a ConvLayer holds (train-flavour and folded forward images, data-gradient images of both flavours, incl. the stem's
     pixel-pair form, strided parity classes and a channel count that is no multiple of 8) after parameters AND BatchNorm tensors changed
     in place: WeightRefresh.run() (2 launches) == images built from scratch, bit for bit; the lazy path then has nothing to rebuild."""
     from ted_spad_amd import engine as E, train_engine as TE
-    items = _layers()
+    items = _layers(dtype)
     folds = {}
     layers = [L for L, _, _ in items]
     for L, bn, xd in items:
@@ -106,12 +107,13 @@ def test_refreshed_images_equal_a_fresh_pack():
     assert TE.IMAGES_GEN == gen and R.run() is False           # the lazy path found every image fresh
 
 
-def test_refresh_follows_parameters_whose_storage_moved():
+@pytest.mark.parametrize("dtype", ("f16", "bf16"))
+def test_refresh_follows_parameters_whose_storage_moved(dtype):
     """A parameter or BatchNorm tensor that MOVED (`p.data = ...`, a `.to()` / dtype round trip, an EMA swap) since the job tables were built: the refresh must
     read the new storage -- the cached tables hold the old addresses (possibly freed memory) -- and the images must equal a fresh pack of the new values
     (round-2 advisor finding: the tables were reused and the stale images then stamped as fresh)."""
     from ted_spad_amd import engine as E, train_engine as TE
-    items = _layers()[1:4]
+    items = _layers(dtype)[1:4]
     folds = {}
     layers = [L for L, _, _ in items]
     for L, bn, xd in items:

@@ -582,3 +582,147 @@ def test_layout_table_and_reference():
         for ch in range(3):
             assert torch.equal(y[..., ch], x[:, ch])
         assert torch.equal(y.reshape(2, 2, 3, 2, 2 * cpad)[..., cpad:cpad + 3], x.permute(0, 2, 3, 4, 1)[:, :, :, 1::2])        # cpad 4: the pair's second pixel
+
+
+# ---- the weight-image references of tests/test_hip_pack_exact.py ------------------------------------------------------------------------------------------------
+PACK_SEED = 3
+PACK_IDS = [c.name for c in R.PACK_CASES]
+
+
+@pytest.mark.parametrize("dtype", R.BOTH)
+def test_round16_bits_equals_torchs_conversion(dtype):
+    """round16_bits (numpy float16 / integer arithmetic on the fp32 bits) against torch's fp32 -> 16-bit cast: random values over the whole range of the type,
+    every planted value, every tie of a binade, subnormals and both zeros."""
+    u = synth_tensor(7, "r16", (200000,), -1, 1).numpy().astype(np.float32)
+    e = synth_tensor(7, "r16e", (200000,), -30, 15.9).numpy()
+    step = 2.0 ** -11 if dtype == "f16" else 2.0 ** -8
+    ties = (1.0 + step * np.arange(1, 2 ** 12, 2)).astype(np.float32)
+    v = np.concatenate([u, (u * 2.0 ** e).astype(np.float32), R.PACK_PLANTS, -R.PACK_PLANTS, ties, -ties, np.array([0.0, -0.0, 65504.0, -65504.0], dtype=np.float32)])
+    t = torch.from_numpy(v)
+    want = (t.clamp(-R.F16_MAX, R.F16_MAX) if dtype == "f16" else t).to(R.TDT[dtype]).view(torch.int16).numpy()
+    assert np.array_equal(R.round16_bits(v, dtype), want)
+    assert np.array_equal(R._once_from_exact(v.astype(np.float64), dtype), want)        # an fp32 value rounded "from exact" is the same single rounding
+
+
+def _host_packed(w5, case, dtype):
+    from ted_spad_amd import engine as E
+    return E.PackedConv(torch.from_numpy(w5), None, None, stride=case.stride, dtype=dtype, device="cpu", pair_w=case.pair_w)
+
+
+@pytest.mark.parametrize("dtype", R.BOTH)
+@pytest.mark.parametrize("case", R.PACK_CASES, ids=PACK_IDS)
+def test_pack_fwd_image_equals_the_host_packing(case, dtype):
+    """pack_image_ref mode 0 == the bits of engine.PackedConv(..., device="cpu").w (torch permute / stem_pair_form, written independently), padded as the library
+    pads, with weights that round (ties, subnormals, -0.0). The host packing neither takes a scale nor saturates f16: it gets the fp32 product, clamped to +-65504."""
+    w, s = R.pack_weights(case.shape, PACK_SEED)
+    for scale in (None, s):
+        p = w if scale is None else w * scale.reshape(-1, 1, 1, 1, 1)
+        pc = _host_packed(np.clip(p, -R.F16_MAX, R.F16_MAX) if dtype == "f16" else p, case, dtype)
+        a = case.pack_args(0)
+        assert (pc.cpad, pc.kpad) == (a["rows_pad"], a["kpad"]) and (pc.cin, pc.k) == (case.cink, case.k_k)
+        img = R.pack_image_ref(w, scale, dtype=dtype, **a)
+        assert img.shape == (pc.cpad, pc.kpad) and img.dtype == np.int16
+        assert np.array_equal(img, pc.w.view(torch.int16).numpy())
+
+
+@pytest.mark.parametrize("dtype", R.BOTH)
+@pytest.mark.parametrize("case", R.PACK_CASES, ids=PACK_IDS)
+def test_pack_dgrad_image_equals_the_flipped_transposed_forward_image(case, dtype):
+    """pack_image_ref mode 1 against a second formulation: the parity class (ct, ch, cw) of strides (st, sh, sw) is the kernel-form weight sub-sampled
+    [ct::st, ch::sh, cw::sw], its three tap axes flipped and co exchanged with ci -- whose FORWARD image over co8 channels is the data-gradient image
+    (stride 1: the textbook flipped, transposed kernel). The per-co scale is multiplied in first (one fp32 multiply either way)."""
+    from ted_spad_amd import engine as E
+    w, s = R.pack_weights(case.shape, PACK_SEED)
+    classes = case.classes()
+    assert sorted(g[0] * g[1] * g[2] for g in classes) == sorted(case.class_taps)
+    assert sum(g[0] * g[1] * g[2] for g in classes) == case.k_k[0] * case.k_k[1] * case.k_k[2]            # every kernel-form tap in exactly one class
+    for scale in (None, s):
+        p = w if scale is None else w * scale.reshape(-1, 1, 1, 1, 1)
+        wkf = E.stem_pair_form(torch.from_numpy(p), case.pair_w)[0].numpy() if case.pair_w is not None else p
+        for geo in classes:
+            Et, Eh, Ew, ct, ch, cw, st, sh, sw = geo
+            sub = np.ascontiguousarray(wkf[:, :, ct::st, ch::sh, cw::sw][:, :, ::-1, ::-1, ::-1].swapaxes(0, 1))
+            assert sub.shape[2:] == (Et, Eh, Ew)
+            a = case.pack_args(1, geo)
+            want = R.pack_image_ref(sub, None, cink=case.co8, kwk=Ew, pair_shift=-1, mode=0, rows=sub.shape[0], rows_pad=a["rows_pad"], kpad=a["kpad"], geo=None, dtype=dtype)
+            assert np.array_equal(R.pack_image_ref(w, scale, dtype=dtype, **a), want), geo
+
+
+@pytest.mark.parametrize("case", R.PACK_CASES, ids=PACK_IDS)
+def test_pack_cases_take_the_path_named_in_their_row(case):
+    """pk_plan_ref per case: LDS tiles or pack_body, rows / channels per tile, more tiles than a job's 256 workgroups, chunks of the last co tile."""
+    a = case.pack_args(0)
+    q = case.plan(0)
+    assert (q.tiled, q.per_tile, q.tiled and q.tiles > R.PK_MAX_BLOCKS) == case.fwd
+    assert q.blocks(a["rows_pad"], a["kpad"]) == (min(q.tiles, 256) if q.tiled else min(256, (a["rows_pad"] * a["kpad"] // 8 + 1023) // 1024))
+    for geo in case.classes():
+        q = case.plan(1, geo)
+        assert (q.tiled, q.per_tile, q.tiled and q.tiles > R.PK_MAX_BLOCKS) == case.dgrad
+        if q.tiled:
+            assert (case.co8 - 1) % 64 // 8 + 1 == case.last_chunks
+            a = case.pack_args(1, geo)
+            assert a["kpad"] >= geo[0] * geo[1] * geo[2] * case.co8 and a["rows_pad"] > a["rows"]             # rows above `rows` exist: the tiles' zero rows are checked
+
+
+def test_pack_table_reaches_every_branch_of_the_plan():
+    by = {c.name: c for c in R.PACK_CASES}
+    co, ci, kt, kh, kw = by["longest_tiled_row"].shape
+    assert ci * kt * kh * kw == R.PK_FLOATS - 1 and ci % 8 != 0
+    co, ci, kt, kh, kw = by["row_too_long"].shape
+    assert R.PK_FLOATS < ci * kt * kh * kw <= R.PK_FLOATS + 8
+    co, ci, kt, kh, kw = by[R.PACK_BIG].shape
+    assert ci * kt * kh * kw > R.PK_FWD_FLOATS and by[R.PACK_BIG].plan(0).blocks(*by[R.PACK_BIG].image_dims(0)[1:]) == 256
+    assert {c.fwd for c in R.PACK_CASES} >= {R.BODY, (True, 1, True), (True, 1, False), (True, 64, True), (True, 64, False), (True, 11, False)}
+    assert {c.dgrad for c in R.PACK_CASES} >= {R.BODY, (True, 8, False), (True, 8, True), (True, 16, False), (True, 32, False), (True, 32, True)}
+    assert any(c.dgrad == R.BODY and c.pair_w is None for c in R.PACK_CASES) and any(c.pair_w is not None for c in R.PACK_CASES)
+    assert {c.last_chunks for c in R.PACK_CASES if c.co8 > 64} >= {1, 2, 4, 6}                             # a last co tile with fewer than 8 chunks
+    assert any(c.dgrad[0] and c.shape[1] < c.dgrad[1] for c in R.PACK_CASES)                                # ci below the channels of one tile
+    assert any(c.dgrad[0] and c.shape[1] % c.dgrad[1] and c.shape[1] > c.dgrad[1] for c in R.PACK_CASES)    # a last channel tile partly filled
+    assert [R.find_job_rounds(n) for n in R.FIND_JOB_SIZES] == [0, 1, 1, 1, 2, 2, 2, 3]
+
+
+@pytest.mark.parametrize("dtype", R.BOTH)
+def test_pack_weights_hold_every_rounding_ingredient(dtype):
+    """Per case, with and without the scale: a tie above an even and above an odd mantissa, an f16-subnormal value, -0.0, a value above 65504, nothing non-finite.
+    A product w * scale whose fp32 rounding changes the 16-bit result (a pack that rounded once would differ) needs ~2^13 (f16) / 2^16 (bf16) products to occur:
+    asserted for the largest case, which both entry points and the find_job tables pack."""
+    for case in R.PACK_CASES:
+        w, s = R.pack_weights(case.shape, PACK_SEED)
+        assert bool(np.isfinite(w).all() and np.isfinite(s).all()) and int((s == 1).sum()) >= 2 and int((s < 0).sum()) >= 1
+        for scale in (None, s):
+            got = R.rounding_ingredients(w, scale, dtype)
+            for key in ("tie_even", "tie_odd", "f16_subnormal", "neg_zero", "above_f16_max"):
+                assert got[key] >= 1, (case.name, key)
+            assert (got["double_rounding"] == 0) if scale is None else (got["double_rounding"] >= 1 or case.name != R.PACK_BIG), case.name
+    # the planted ties round as round-to-nearest-even says, and differently under truncation or round-half-up
+    tie = {"f16": 2.0 ** -11, "bf16": 2.0 ** -8}[dtype]
+    v = np.array([1 + tie, 1 + 3 * tie], dtype=np.float32)
+    assert np.array_equal(R.round16_bits(v, dtype), R.round16_bits(np.array([1.0, 1 + 4 * tie], dtype=np.float32), dtype))
+    big = R.round16_bits(np.array([70000.0, 65520.0], dtype=np.float32), dtype).view(np.uint16)
+    assert list(big) == ([0x7BFF, 0x7BFF] if dtype == "f16" else [0x4789, 0x4780])
+
+
+def test_fold_and_unpack_refs_equal_the_host_formulas():
+    """fold_ref64 == engine.fold_bn's host branch (torch float64), bit for bit after the fp32 rounding; wgrad_unpack_ref == the view ConvLayer.flush_grad takes."""
+    from ted_spad_amd import engine as E
+    for C in R.FOLD_C:
+        g, be, m, v, cb = R.fold_inputs(C, 11)
+        assert int((g < 0).sum()) >= (C > 1) and int((v == 0).sum()) >= 1
+        for bias in (None, cb):
+            for eps in (1e-5, 1e-3):
+                sc, sh = R.fold_ref64(g, be, m, v, eps, bias)
+                ts, tb = E.fold_bn(*(torch.from_numpy(t) for t in (g, be, m, v)), eps, conv_bias=None if bias is None else torch.from_numpy(bias))
+                assert np.array_equal(sc.astype(np.float32), ts.numpy()) and np.array_equal(sh.astype(np.float32), tb.numpy())
+                assert bool((np.abs(sh.astype(np.float32).astype(np.float64) - sh) <= R.fold_shift_bound(sh, be, m, sc, bias)).all())
+    sc, sh = R.fold_ref64(None, None, None, None, 0.0, cb)
+    assert np.array_equal(sc, np.ones(len(cb))) and np.array_equal(sh, cb.astype(np.float64))
+    sc, sh = R.fold_ref64(None, None, None, None, 0.0, None, n=5)
+    assert np.array_equal(sc, np.ones(5)) and np.array_equal(sh, np.zeros(5))
+    assert list(R.ulp32(np.array([1.0, 1.5, 2.0, 0.75, 0.0, 1e-46]))) == [2.0 ** -23, 2.0 ** -23, 2.0 ** -22, 2.0 ** -24, 2.0 ** -149, 2.0 ** -149]
+    co, ci, k, cink = 5, 3, (1, 3, 3), 8
+    kpad = 128
+    dw = torch.from_numpy(R.small_ints(13, "dwp", (128, kpad), -8, 8, density=1.0).numpy().astype(np.float32))
+    rs = np.array([0.5, 2.0, 1.0, 4.0, 0.25])
+    view = dw[:co, :9 * cink].view(co, 1, 3, 3, cink).permute(0, 4, 1, 2, 3)[:, :ci] * torch.from_numpy(rs).float().view(-1, 1, 1, 1, 1)
+    g0 = np.arange(co * ci * 9, dtype=np.float64).reshape(co, ci, 1, 3, 3)
+    assert np.array_equal(R.wgrad_unpack_ref(dw.numpy(), co, ci, k, cink, kpad, rs, g0), view.double().numpy() + g0)
