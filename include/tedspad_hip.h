@@ -578,7 +578,38 @@ int32_t tedspad_clip_augment(const void *blob_host, void *blob_dev, int64_t blob
                              int64_t luts_off, int32_t nluts, float *out, int64_t out_elems, int32_t oh, int32_t ow, int64_t so_c, int64_t so_h,
                              int64_t so_w, void *stream);
 
-/* MGFN feature feed (anomaly_detection_mgfn/datasets/dataset.py:65-100): feat (T, ncrops, F) fp32.
+/* The VISPR loaders' per-image augmentation (aux_code/vispr_dl.py: vispr_dataset.augmentation :71-129, vispr_ssl_dataset.augmentation :186-251) for a whole
+ * ragged batch in ONE launch: contiguous uint8 (3,H,W) image (torchvision.io.read_image's layout) -> resized_crop (crop, zero-filled right of and below the
+ * image, + ATen's antialiased bilinear resize on fp32: width pass, height pass, one rounding half to even) -> contrast / hue / saturation / brightness /
+ * contrast / grayscale + gamma (torchvision's TENSOR path: fp32 _blend and RGB->HSV->RGB truncated to a byte after every op) -> hflip -> one erased box ->
+ * / 255 -> fp32 out[dst + c*so_c + y*so_h + x*so_w]. One record per OUTPUT image; two records may name the same source (the two SSL views). The blob is laid
+ * out as in tedspad_clip_augment, with tedspad_image_record records, tables of (2 + taps) words {first index, count, fp32 weights}
+ * (tedspad_resize_aa_table) and 256-byte gamma tables the caller builds. `scratch` holds the fp32 width-pass intermediate: record i owns the
+ * 3 * min(ch, H - top) * ow floats at `tmp`, slices must not overlap. Everything is checked on the host before the launch. Limits: 3*oh*ow bytes must fit the
+ * LDS (224 x 224), sources up to 16384 x 16384, crop boxes up to 4096 x 4096; beyond them TEDSPAD_EUNSUPPORTED, nothing is clamped. The resize equals torch's
+ * bit for bit at dyadic scales and elsewhere except where torch's own fp32 value lies at a rounding tie; the colour chain is bit-exact
+ * (tests/test_hip_vispr_augment.py). Flags: TEDSPAD_AUG_* above, without TEDSPAD_AUG_REVERSE. */
+typedef struct tedspad_image_record {
+    const uint8_t *src;                 /* the (3, H, W) uint8 source image */
+    int64_t dst;                        /* element offset of the output image in `out` */
+    int64_t tmp;                        /* element offset of this record's width-pass intermediate in `scratch` */
+    int32_t H, W;
+    int32_t top, left, ch, cw;          /* crop box; top + ch > H and left + cw > W are allowed (zero fill), negative origins are not */
+    int32_t ytab, xtab, ytaps, xtaps;   /* the two tables: word offsets and taps per row */
+    int32_t flags;                      /* TEDSPAD_AUG_* */
+    int32_t gamma_lut;                  /* index of the 256-byte table of adjust_gamma */
+    float contrast, contrast_1m;        /* _blend's ratio and (1.0 - ratio), the latter formed in double and then rounded, as Python does */
+    float saturation, saturation_1m;
+    float brightness, brightness_1m;
+    float hue;                          /* hue_factor in [-0.5, 0.5] */
+    int32_t erase[4];                   /* one box {i (row), j (column), h, w}; h <= 0 or w <= 0: none. Clipped at the borders like a slice */
+    int32_t reserved;
+} tedspad_image_record;
+int32_t tedspad_image_augment(const void *blob_host, void *blob_dev, int64_t blob_bytes, int32_t nrec, int64_t tables_off, int64_t table_words,
+                              int64_t luts_off, int32_t nluts, float *scratch, int64_t scratch_elems, float *out, int64_t out_elems, int32_t oh,
+                              int32_t ow, int64_t so_c, int64_t so_h, int64_t so_w, void *stream);
+
+/* MGFN feature feed(anomaly_detection_mgfn/datasets/dataset.py:65-100): feat (T, ncrops, F) fp32.
  * length > 0 (train): out (ncrops, length, F+1) = process_feat (utils/utils.py:34-42: means over the
  * numpy.linspace(0,T,length+1,dtype=int) segments, a single row where a segment is empty) + L2 magnitude channel.
  * length == 0 (test_mode): out (T, ncrops, F+1) = the rows + magnitude channel. */

@@ -122,6 +122,7 @@ SYMBOLS = {
     "tedspad_frames_crop_resize_tp": (_I32, [_P] + [_I32] * 16 + [_P, _P, C.c_float, _I32, _P] + [_I32] * 4 + [_P]),
     "tedspad_frames_crop_resize_pil": (_I32, [_P] + [_I32] * 10 + [_P, _I32, _P, _I32, _P] + [_I64] * 4 + [_P]),
     "tedspad_clip_augment": (_I32, [_P, _P, _I64, _I32, _I64, _I64, _I64, _I32, _P, _I64, _I32, _I32, _I64, _I64, _I64, _P]),
+    "tedspad_image_augment": (_I32, [_P, _P, _I64, _I32, _I64, _I64, _I64, _I32, _P, _I64, _P, _I64, _I32, _I32, _I64, _I64, _I64, _P]),
     "tedspad_segment_pool_mag":(_I32, [_P, _I32, _I32, _I32, _I32, _P, _P]),
     "tedspad_count_saturated": (_I32, [_P, _I64, _I32, _I32, _I32, _P, _P]),
     "tedspad_mgfn_ln_stats": (_I32, [_P, _I32, _I32, _I32, C.c_float, _I32, _P, _P]),
