@@ -755,6 +755,28 @@ int32_t tedspad_minmax_ws_floats(void);
 int32_t tedspad_minmax_f32(const float *x, int64_t n, float *ws, float *out2, void *stream);
 int32_t tedspad_video_frames_u8(const float *x, const float *minmax, uint8_t *out, int32_t T, int32_t H, int32_t W, void *stream);
 
+/* ---- nn.L1Loss() and its gradient: fa_pretraining/train_reconstruction.py:46-47,77 (`criterion(output, inputs)`, `loss.backward()`) ----
+ * Both forms: *loss = mean |y - x| (0-d fp32), every reduction in a fixed order without atomics (bit-identical from run to run); two launches (the terms and
+ * per-workgroup partials, then the mean). ws: fp32[tedspad_l1_ws_floats()] workspace. The gradient magnitude is g = grad_scale / (float)numel, one fp32
+ * division on the host; an element's gradient is +g, -g, exactly 0 where y == x (torch.sign) and NaN where the difference is NaN.
+ * A lane of the first launch adds ceil(items / (blocks * tedspad_l1_block_threads())) items in sequence, blocks = min(ceil(items / threads),
+ * tedspad_l1_max_blocks()); everything after that is a binary tree (items: pixel records of 3 terms each in the train form, elements in the flat form).
+ *
+ * tedspad_l1_loss_grad_cl (train form): y = the head's 16-bit channels-last output, n * hw pixel records of 8 channels `ld` elements apart (ld >= 8), channels
+ * 0-2 valid; x = the fp32 (n,3,hw) target. dl = the 16-bit (n,hw,8) gradient records ConvLayer.wgrad / dgrad read: channels 0-2 = sign(float(y) - x) * g with g
+ * rounded once to the storage type (round to nearest even), channels 3-7 = 0, one 16-byte store each (dl 16-byte aligned). y32 (may be NULL): the fp32 (n,3,hw)
+ * copy of y. numel = n * 3 * hw.
+ * tedspad_l1_loss_flat: y, x contiguous fp32 of numel elements in any (common) layout; dy (may be NULL) = sign(y - x) * g in fp32. (c, hw) only choose the ORDER of
+ * the sum: c = 1, hw = numel adds in index order; for (n,c,hw) arrays, c and hw make an item of the c values of one pixel -- with c = 3 the partition and order
+ * of the train form, whose loss this then equals bit for bit on the same values. numel must be a multiple of c * hw. */
+int32_t tedspad_l1_block_threads(void);
+int32_t tedspad_l1_max_blocks(void);
+int32_t tedspad_l1_ws_floats(void);
+int32_t tedspad_l1_loss_grad_cl(const void *y, int32_t ld, const float *x, void *dl, float *y32, float *ws, float *loss, int32_t n, int64_t hw,
+                                float grad_scale, int32_t dtype, void *stream);
+int32_t tedspad_l1_loss_flat(const float *y, const float *x, float *dy, float *ws, float *loss, int64_t numel, int32_t c, int64_t hw, float grad_scale,
+                             void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -154,6 +154,11 @@ SYMBOLS = {
     "tedspad_minmax_ws_floats": (_I32, []),
     "tedspad_minmax_f32": (_I32, [_P, _I64, _P, _P, _P]),
     "tedspad_video_frames_u8": (_I32, [_P, _P, _P, _I32, _I32, _I32, _P]),
+    "tedspad_l1_block_threads": (_I32, []),
+    "tedspad_l1_max_blocks": (_I32, []),
+    "tedspad_l1_ws_floats": (_I32, []),
+    "tedspad_l1_loss_grad_cl": (_I32, [_P, _I32, _P, _P, _P, _P, _P, _I32, _I64, C.c_float, _I32, _P]),
+    "tedspad_l1_loss_flat": (_I32, [_P, _P, _P, _P, _P, _I64, _I32, _I64, C.c_float, _P]),
 }
 
 _lib = None

@@ -2,6 +2,7 @@
 
     save_anonymizer_checkpoint(path, epoch, fa, fb, ft, optimizers=None)   anonymization_training/train_anonymizer.py:511-550
     save_action_checkpoint(path, epoch, ft, optimizer, loss_scale)         action_training/train_anonymized_action.py:388-414
+    save_reconstruction_checkpoint(path, epoch, lr_counter, fa, optimizer) fa_pretraining/train_reconstruction.py:179-196
 
 `epoch` is stored as `epoch + 1`, as the scripts do. The action script stores its `GradScaler` object under 'amp_scaler'; this build has a
 static loss scale and no GradScaler, so the key holds the plain dict {'scale': loss_scale} (a file torch.load reads with weights_only=True).
@@ -25,6 +26,19 @@ def save_anonymizer_checkpoint(path, epoch, fa, fb, ft, optimizers=None):
         states["optimizer_fa"] = opt_fa.state_dict()
         states["optimizer_fb"] = opt_fb.state_dict()
         states["optimizer_ft"] = opt_ft.state_dict()
+    torch.save(states, path)
+    return states
+
+
+def save_reconstruction_checkpoint(path, epoch, lr_counter, fa, optimizer):
+    """`model_temp.pth` / the best-validation file of fa_pretraining/train_reconstruction.py:179-196: what `load_fa_model(saved_model_file=...)`
+    (and train_anonymizer.py through it) starts from."""
+    states = {
+        "epoch": epoch + 1,
+        "lr_counter": lr_counter,
+        "fa_model_state_dict": fa.state_dict(),
+        "optimizer": optimizer.state_dict(),
+    }
     torch.save(states, path)
     return states
 

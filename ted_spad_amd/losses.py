@@ -6,6 +6,7 @@ gradients, which `backward` scales by the incoming gradient.
     TripletMarginLoss(margin=1.0)(anchor, positive, negative)                       train_anonymizer.py:349-350,115
     CrossEntropyLoss()(logits, labels)                                              train_anonymizer.py:347,107
     BCEWithLogitsLoss()(logits, targets)                                            privacy_training/train_privacy.py:157,52
+    L1Loss()(output, inputs)                                                        fa_pretraining/train_reconstruction.py:111,46
 
 The reference re-instantiates NTXentLoss (and rebuilds its numpy mask) every iteration
 (train_anonymizer.py:82,155); here the mask is in-kernel.
@@ -125,6 +126,72 @@ class _BCEFn(torch.autograd.Function):
     def backward(ctx, g):
         (dl,) = ctx.saved_tensors
         return (dl * g).view(ctx.shape), None
+
+
+def _l1_ws(device):
+    return torch.empty(_lib.lib().tedspad_l1_ws_floats(), dtype=torch.float32, device=device)
+
+
+def l1_flat(y, x, grad_scale=None):
+    """mean |y - x| of two fp32 tensors of one shape (any layout, made contiguous) as a 0-d fp32 device tensor, in a fixed summation order
+    (tedspad_l1_loss_flat). With grad_scale also dy = sign(y - x) * fp32(grad_scale / numel), shaped like y: returns (loss, dy).
+    An (n,3,h,w) pair -- images -- is added pixel by pixel, the order of `l1_train`: on the same values the two give the same bits."""
+    require_cuda(y, "L1Loss")
+    if y.shape != x.shape or y.numel() == 0:
+        raise ValueError("L1Loss: input %s and target %s must have the same non-empty shape" % (tuple(y.shape), tuple(x.shape)))
+    yc, xc = _f32(y), _f32(x)
+    c, hw = (3, yc.shape[2] * yc.shape[3]) if yc.dim() == 4 and yc.shape[1] == 3 else (1, yc.numel())
+    loss = torch.empty(1, dtype=torch.float32, device=yc.device)
+    dy = torch.empty_like(yc) if grad_scale is not None else None
+    _lib.check(_lib.lib().tedspad_l1_loss_flat(yc.data_ptr(), xc.data_ptr(), dy.data_ptr() if dy is not None else None, _l1_ws(yc.device).data_ptr(),
+                                               loss.data_ptr(), yc.numel(), c, hw, C.c_float(grad_scale or 0.0), _stream_ptr()), "tedspad_l1_loss_flat")
+    return loss[0] if dy is None else (loss[0], dy)
+
+
+def l1_train(y, x, grad_scale, want_y32=False):
+    """The train form (tedspad_l1_loss_grad_cl): y = the 16-bit channels-last Act of a 3-channel output (8-channel records, t == 1), x = the fp32
+    (n,3,h,w) target. Returns (loss 0-d fp32, dl: the (n,1,h,w,8) gradient Act with sign(float(y) - x) * grad_scale / numel in channels 0-2,
+    y32: the fp32 NCHW copy of y or None)."""
+    from .engine import Act
+    n, t, h, w = y.dims
+    if t != 1 or tuple(x.shape) != (n, 3, h, w) or x.dtype != torch.float32 or not x.is_cuda:
+        raise ValueError("l1_train: y is (%d,%d,%d,%d,8) channels-last, the target must be fp32 cuda (%d,3,%d,%d), got %s %s"
+                         % (n, t, h, w, n, h, w, tuple(x.shape), x.dtype))
+    xc = x.contiguous()
+    dl = Act.empty(n, 1, h, w, 8, y.buf.dtype, y.buf.device)
+    loss = torch.empty(1, dtype=torch.float32, device=y.buf.device)
+    y32 = torch.empty_like(xc) if want_y32 else None
+    code = _lib.F16 if y.buf.dtype == torch.float16 else _lib.BF16
+    _lib.check(_lib.lib().tedspad_l1_loss_grad_cl(y.ptr, y.ld, xc.data_ptr(), dl.ptr, y32.data_ptr() if want_y32 else None, _l1_ws(xc.device).data_ptr(),
+                                                  loss.data_ptr(), n, h * w, C.c_float(grad_scale), code, _stream_ptr()), "tedspad_l1_loss_grad_cl")
+    return loss[0], dl, y32
+
+
+class _L1Fn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, y, target):
+        loss, dy = l1_flat(y, target, grad_scale=1.0)
+        ctx.save_for_backward(dy)
+        ctx.shape = y.shape
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        (dy,) = ctx.saved_tensors
+        return (dy * g).view(ctx.shape), None
+
+
+class L1Loss(nn.Module):
+    """nn.L1Loss() with its default mean reduction (fa_pretraining/train_reconstruction.py:111,46): value and d(loss)/d(input) = sign(input - target) / numel
+    from the flat form of the L1 kernel. No gradient w.r.t. the target (the script's target is its data)."""
+
+    def __init__(self, size_average=None, reduce=None, reduction="mean"):
+        super().__init__()
+        if size_average is not None or reduce is not None or reduction != "mean":
+            raise NotImplementedError("L1Loss: only the default mean reduction is built; train_reconstruction.py:111 uses nothing else")
+
+    def forward(self, input, target):
+        return _L1Fn.apply(input, target)
 
 
 class BCEWithLogitsLoss(nn.Module):

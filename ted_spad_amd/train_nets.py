@@ -743,8 +743,9 @@ class UNetPPTrainer:
         b.append([self.stem.weight, self.stem_bn.weight, self.stem_bn.bias])
         return b
 
-    def forward(self, x: torch.Tensor):
-        """x: (N,3,H,W) fp32, H and W multiples of 16 -> (y (N,3,H,W) fp32 (no activation), tape)."""
+    def forward(self, x: torch.Tensor, nchw: bool = True):
+        """x: (N,3,H,W) fp32, H and W multiples of 16 -> (y (N,3,H,W) fp32 (no activation), tape). nchw=False: y stays the head's 16-bit
+        channels-last Act (N,1,H,W,8), first 3 channels valid -- for a loss kernel that reads it in place (pretrain.ReconstructionTrainStep)."""
         from .unetpp import UnetPlusPlus as U
         m = self.m
         E.require_cuda(x, "UNetPPTrainer")
@@ -809,11 +810,12 @@ class UNetPPTrainer:
         tape["x03"] = x03
         y = self.head.forward(x03, relu=False)
         TE.flush_counters()
-        return E.act_to_nchw(y, 3).squeeze(2), tape
+        return (E.act_to_nchw(y, 3).squeeze(2) if nchw else y), tape
 
-    def backward(self, tape, dy: torch.Tensor, on_bucket_done=None):
+    def backward(self, tape, dy: Optional[torch.Tensor] = None, on_bucket_done=None, dl: Optional[Act] = None):
         """dy: (N,3,H,W) fp32 gradient w.r.t. the output; accumulates every on-path parameter's .grad.
-        on_bucket_done(k): the k-th group of `grad_buckets()` is final and flushed (last backward pass of a step only)."""
+        on_bucket_done(k): the k-th group of `grad_buckets()` is final and flushed (last backward pass of a step only).
+        dl (instead of dy): the same gradient already as the 16-bit (N,1,H,W,8) Act the head's wgrad / dgrad read (channels 3-7 zero)."""
         n, H, W = tape["n"], tape["H"], tape["W"]
         code = _lib.F16 if self.m.compute_dtype == "f16" else _lib.BF16
         G = {}
@@ -844,7 +846,12 @@ class UNetPPTrainer:
                 TE.flush_conv_grads(layers)
                 on_bucket_done(k)
 
-        dl = TE.nchw_grad_to_act(dy, None, (1, H, W), dtype=self.m.compute_dtype)
+        if (dy is None) == (dl is None):
+            raise ValueError("UNetPPTrainer.backward takes the output gradient once: dy (fp32 NCHW) or dl (16-bit Act)")
+        if dl is None:
+            dl = TE.nchw_grad_to_act(dy, None, (1, H, W), dtype=self.m.compute_dtype)
+        elif dl.dims != (n, 1, H, W) or dl.c != 8 or dl.ld != 8 or dl.buf.dtype != tape["x03"].buf.dtype:
+            raise ValueError("UNetPPTrainer.backward: dl must be the (%d,1,%d,%d,8) %s Act of this tape" % (n, H, W, tape["x03"].buf.dtype))
         x03 = tape["x03"]
         self.head.wgrad(x03, dl)
         d = self.head.dgrad(dl, x03.dims[1:])
