@@ -541,6 +541,24 @@ int32_t tedspad_frames_crop_resize_pil(const void *frames, int32_t T, int32_t H,
                                        int32_t cw, int32_t oh, int32_t ow, const int32_t *ytab, int32_t ytaps, const int32_t *xtab,
                                        int32_t xtaps, float *out, int64_t so_t, int64_t so_c, int64_t so_h, int64_t so_w, void *stream);
 
+/* Decoded frames -> the ANONYMIZER's input activation (the extraction scripts run fa on every frame: dali_extraction.py:169-173, st_feature_extraction.py:24-26).
+ * The clip sampling of tedspad_frames_crop_resize_tp (clip i, frame f = source frame first + i*clip_step + f*frame_step; an index >= T is a zero frame, stored
+ * as zeros), each frame / divisor -> crop -> antialiased resize (-> flip) as tedspad_frames_crop_resize, written as output frame i*t_clip + f of the 16-bit
+ * channels-last activation tedspad_clip_to_channels_last builds from the fp32 frames: cpad = 4 -> (frames, oh, ow/2, 8) pixel pairs {c0 c1 c2 0 | c0 c1 c2 0}
+ * (ow even), cpad = 8 -> (frames, oh, ow, 8), channels >= C zero. `act` 16-byte aligned, n_clips * t_clip * oh < 2^31. Bit-identical to
+ * tedspad_frames_crop_resize followed by tedspad_clip_to_channels_last; no fp32 frame is written. */
+int32_t tedspad_frames_crop_resize_act(const void *frames, int32_t in_is_float, int32_t T, int32_t H, int32_t W, int32_t C, int32_t n_clips,
+                                       int32_t first, int32_t clip_step, int32_t frame_step, int32_t t_clip, int32_t y0, int32_t x0, int32_t ch,
+                                       int32_t cw, int32_t oh, int32_t ow, const int32_t *ytab, const int32_t *xtab, float divisor, int32_t flip,
+                                       void *act, int32_t cpad, int32_t dtype, void *stream);
+
+/* The same sampling and output with the arithmetic of tedspad_frames_crop_resize_pil (uint8 frames, Pillow's two-pass fixed-point resample, / 255):
+ * bit-identical to tedspad_frames_crop_resize_pil followed by tedspad_clip_to_channels_last. */
+int32_t tedspad_frames_crop_resize_pil_act(const void *frames, int32_t T, int32_t H, int32_t W, int32_t C, int32_t n_clips, int32_t first,
+                                           int32_t clip_step, int32_t frame_step, int32_t t_clip, int32_t y0, int32_t x0, int32_t ch, int32_t cw,
+                                           int32_t oh, int32_t ow, const int32_t *ytab, int32_t ytaps, const int32_t *xtab, int32_t xtaps,
+                                           void *act, int32_t cpad, int32_t dtype, void *stream);
+
 /* The training loaders' per-frame augmentation (aux_code/ucf101_dl.py: contrastive_train_dataloader.augmentation :596-630 / weak_augmentation :632-642,
  * single_train_dataloader.augmentation :149-183) for a whole batch in ONE launch: uint8 (H,W,3) frame -> resized_crop (Pillow crop, zero-filled right of and
  * below the frame, + two-pass BILINEAR resize, as tedspad_frames_crop_resize_pil) -> contrast / hue / saturation / brightness / contrast / grayscale + gamma

@@ -121,6 +121,8 @@ SYMBOLS = {
     "tedspad_frames_crop_resize": (_I32, [_P] + [_I32] * 11 + [_P, _P, C.c_float, _I32, _P] + [_I64] * 4 + [_P]),
     "tedspad_frames_crop_resize_tp": (_I32, [_P] + [_I32] * 16 + [_P, _P, C.c_float, _I32, _P] + [_I32] * 4 + [_P]),
     "tedspad_frames_crop_resize_pil": (_I32, [_P] + [_I32] * 10 + [_P, _I32, _P, _I32, _P] + [_I64] * 4 + [_P]),
+    "tedspad_frames_crop_resize_act": (_I32, [_P] + [_I32] * 16 + [_P, _P, C.c_float, _I32, _P] + [_I32] * 2 + [_P]),
+    "tedspad_frames_crop_resize_pil_act": (_I32, [_P] + [_I32] * 15 + [_P, _I32, _P, _I32, _P] + [_I32] * 2 + [_P]),
     "tedspad_clip_augment": (_I32, [_P, _P, _I64, _I32, _I64, _I64, _I64, _I32, _P, _I64, _I32, _I32, _I64, _I64, _I64, _P]),
     "tedspad_image_augment": (_I32, [_P, _P, _I64, _I32, _I64, _I64, _I64, _I32, _P, _I64, _P, _I64, _I32, _I32, _I64, _I64, _I64, _P]),
     "tedspad_segment_pool_mag":(_I32, [_P, _I32, _I32, _I32, _I32, _P, _P]),

@@ -81,6 +81,18 @@ __device__ __forceinline__ unsigned load_u8x4(const uint8_t *a, const uint8_t *e
     return w;
 }
 
+// byte / divisor of the kernels that load four bytes at a time (crop_resize_tp_kernel, crop_resize_act_kernel): for 255 without the division or a table --
+// b * fl(1/255) corrected by one residual step is the correctly rounded quotient for every byte value (checked exhaustively in exact arithmetic; tests compare
+// with the dividing kernel bit for bit) -- else from the workgroup's 256-entry table lut[b] = (float)b / div.
+__device__ __forceinline__ float u8_px(unsigned bt, bool div255, const float *lut) {
+    if (div255) {
+        const float xb = (float)bt, r = 1.0f / 255.0f;
+        const float q0 = xb * r;
+        return __builtin_fmaf(__builtin_fmaf(-q0, 255.0f, xb), r, q0);
+    }
+    return lut[bt];
+}
+
 template <typename In> __device__ __forceinline__ float load_px(const In *p, float div);
 template <> __device__ __forceinline__ float load_px<uint8_t>(const uint8_t *p, float div) { return (float)(*p) / div; }
 template <> __device__ __forceinline__ float load_px<float>(const float *p, float div) { return *p / div; }
@@ -189,17 +201,7 @@ __global__ __launch_bounds__(256) void crop_resize_tp_kernel(const ResizeTpKP q)
                 for (int ff = 0; ff < FG; ++ff)
 #pragma unroll
                     for (int k = 0; k < 4; ++k) {
-                        const unsigned bt = (w4[ff] >> (8 * k)) & 255u;
-                        float px;
-                        if (div255) {       // byte / 255.f without the division or a table: b * fl(1/255) corrected by one residual step is the correctly rounded
-                                            // quotient for every byte value (checked exhaustively in exact arithmetic; tests compare with the dividing kernel bit for bit)
-                            const float xb = (float)bt, r = 1.0f / 255.0f;
-                            const float q0 = xb * r;
-                            px = __builtin_fmaf(__builtin_fmaf(-q0, 255.0f, xb), r, q0);
-                        } else {
-                            px = lut[bt];
-                        }
-                        acc[ff][k] += wy[j] * px;
+                        acc[ff][k] += wy[j] * u8_px((w4[ff] >> (8 * k)) & 255u, div255, lut);
                     }
             }
 #pragma unroll
@@ -305,6 +307,127 @@ __global__ __launch_bounds__(256) void crop_resize_pil_kernel(const ResizeU8KP p
         }
         p.out[t * p.so_t + c * p.so_c + oy * p.so_h + ox * p.so_w] = (float)clip8_fixed(acc) / 255.f;   // to_tensor: uint8 -> float / 255
     }
+}
+
+// ------------------------------------------------------------------------------------------------------------
+// Decoded frames -> the ANONYMIZER's input activation (dali_extraction.py:169-173, st_feature_extraction.py:24-26: every frame of every clip goes through fa
+// as an RGB image): HybridValPipe's clip sampling as in crop_resize_tp_kernel, each frame / divisor -> crop -> resize (-> flip), written as the 16-bit
+// channels-last rows tedspad_clip_to_channels_last gives the first conv of UnetPlusPlus (cpad 4: pixel pairs {c0 c1 c2 0 | c0 c1 c2 0}) or UNet (cpad 8:
+// {c0 c1 c2 0 0 0 0 0}); the fp32 frame batch between the two is never written. One workgroup per (output frame, output row): vertical pass into an fp32 LDS
+// row (aa_vpass, or for uint8 frames crop_resize_tp_kernel's four-bytes-per-load form of it on the same u8_px), horizontal pass (aa_hpass) rounded into a 16-bit
+// LDS row, which leaves as 16-byte pieces on consecutive lanes. A source frame outside [0, T) is a zero frame: its rows are stored as zeros.
+// ------------------------------------------------------------------------------------------------------------
+struct ActOutKP {
+    uint4 *act;                 // (frames, oh, ow * cpad / 8) 16-byte pieces
+    int first, clip_step, frame_step, t_clip, cpad;
+};
+
+// the source frame of output frame fo, or -1 for a zero frame
+__device__ __forceinline__ long act_src_frame(const ActOutKP &a, int fo, int T) {
+    const long fr = (long)a.first + (long)(fo / a.t_clip) * a.clip_step + (long)(fo % a.t_clip) * a.frame_step;
+    return fr >= 0 && fr < T ? fr : -1;
+}
+
+// one pixel's channels (v[c], c < 8, zero from C on) rounded to T at pixel slot `ox` of the 16-bit LDS row
+template <typename T>
+__device__ __forceinline__ void act_put_pixel(unsigned char *tile, int cpad, int ox, const float (&v)[8]) {
+    const uint4 pk = pack8<T>(v);
+    if (cpad == 4) reinterpret_cast<uint2 *>(tile)[ox] = make_uint2(pk.x, pk.y);
+    else reinterpret_cast<uint4 *>(tile)[ox] = pk;
+}
+
+// row `orow` (= frame * oh + y) of the activation: `n16` 16-byte pieces from the LDS row, or zeros
+__device__ __forceinline__ void act_store_row(const ActOutKP &a, long orow, int n16, const unsigned char *tile) {
+    uint4 *dst = a.act + orow * n16;
+    for (int i = threadIdx.x; i < n16; i += 256) dst[i] = tile ? reinterpret_cast<const uint4 *>(tile)[i] : make_uint4(0u, 0u, 0u, 0u);
+}
+
+template <typename In, typename T>
+__global__ __launch_bounds__(256) void crop_resize_act_kernel(const ResizeKP p, const ActOutKP a, const uint8_t *in_end) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char lds_act[];
+    const int n16 = p.ow * a.cpad / 8;
+    const int fo = blockIdx.x / p.oh, oy = blockIdx.x % p.oh;
+    const long fr = act_src_frame(a, fo, p.T);
+    if (fr < 0) {                                                    // uniform
+        act_store_row(a, blockIdx.x, n16, nullptr);
+        return;
+    }
+    const int span = p.cw * p.C;
+    float *row = reinterpret_cast<float *>(lds_act + (size_t)n16 * 16);     // [span]
+    float *lut = row + span;                                                // [256] (uint8 input, divisor != 255)
+    const int32_t *ye = p.ytab + (size_t)oy * (2 + p.ytaps);
+    const long rstride = (long)p.W * p.C;
+    const In *base = (const In *)p.in + ((fr * p.H + p.y0 + ye[0]) * p.W + p.x0) * p.C;
+    if constexpr (sizeof(In) == 1) {
+        const bool div255 = p.div == 255.0f;
+        const int yn = ye[1];
+        const float *wy = (const float *)(ye + 2);
+        if (!div255) {                                               // uniform
+            lut[threadIdx.x] = (float)threadIdx.x / p.div;
+            __syncthreads();
+        }
+        for (int g = threadIdx.x; 4 * g < span; g += 256) {          // four consecutive bytes per lane and load, as crop_resize_tp_kernel
+            float acc[4] = {0.f, 0.f, 0.f, 0.f};
+            for (int j = 0; j < yn; j++) {
+                const unsigned w4 = load_u8x4(reinterpret_cast<const uint8_t *>(base) + j * rstride + 4 * g, in_end);
+#pragma unroll
+                for (int k = 0; k < 4; ++k) acc[k] += wy[j] * u8_px((w4 >> (8 * k)) & 255u, div255, lut);
+            }
+#pragma unroll
+            for (int k = 0; k < 4; ++k)
+                if (4 * g + k < span) row[4 * g + k] = acc[k];
+        }
+    } else {
+        aa_vpass<In>(base, rstride, ye, span, p.div, row);
+    }
+    __syncthreads();
+    for (int ox = threadIdx.x; ox < p.ow; ox += 256) {
+        const int32_t *xe = p.xtab + (size_t)ox * (2 + p.xtaps);
+        float v[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int c = 0; c < 3; ++c)
+            if (c < p.C) v[c] = aa_hpass(row, xe, p.C, c);
+        act_put_pixel<T>(lds_act, a.cpad, p.flip ? p.ow - 1 - ox : ox, v);
+    }
+    __syncthreads();
+    act_store_row(a, blockIdx.x, n16, lds_act);
+}
+
+// The same for Pillow's resample (crop_resize_pil_kernel's arithmetic: a lane owns an output pixel and runs the horizontal pass of its temporary rows itself).
+template <typename T>
+__global__ __launch_bounds__(256) void crop_resize_pil_act_kernel(const ResizeU8KP p, const ActOutKP a) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char lds_act[];
+    const int n16 = p.ow * a.cpad / 8;
+    const int fo = blockIdx.x / p.oh, oy = blockIdx.x % p.oh;
+    const long fr = act_src_frame(a, fo, p.T);
+    if (fr < 0) {                                                    // uniform
+        act_store_row(a, blockIdx.x, n16, nullptr);
+        return;
+    }
+    const int32_t *ye = p.ytab + (size_t)oy * (2 + p.ytaps);
+    const int ymin = ye[0], yn = ye[1];
+    const uint8_t *base = p.in + ((fr * p.H + p.y0 + ymin) * p.W + p.x0) * p.C;
+    const long rstride = (long)p.W * p.C;
+    for (int ox = threadIdx.x; ox < p.ow; ox += 256) {
+        const int32_t *xe = p.xtab + (size_t)ox * (2 + p.xtaps);
+        const int xmin = xe[0], xn = xe[1];
+        float v[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            if (c >= p.C) continue;
+            int acc = 1 << 21;
+            for (int j = 0; j < yn; j++) {
+                const uint8_t *r = base + j * rstride + (long)xmin * p.C + c;
+                int hs = 1 << 21;
+                for (int i = 0; i < xn; i++) hs += (int)r[(long)i * p.C] * xe[2 + i];
+                acc += clip8_fixed(hs) * ye[2 + j];
+            }
+            v[c] = (float)clip8_fixed(acc) / 255.f;
+        }
+        act_put_pixel<T>(lds_act, a.cpad, ox, v);
+    }
+    __syncthreads();
+    act_store_row(a, blockIdx.x, n16, lds_act);
 }
 
 // ------------------------------------------------------------------------------------------------------------
@@ -416,6 +539,64 @@ extern "C" int32_t tedspad_frames_crop_resize_tp(const void *frames, int32_t in_
     const char *who = "tedspad_frames_crop_resize_tp";      // (wide source frames (HD) need more than the default 64 KB of dynamic LDS)
     if (in_is_float) TS_WITH_T(dtype, return launch_lds<crop_resize_tp_kernel<float, T>>(who, g, dim3(256), lds, s, q));
     TS_WITH_T(dtype, return launch_lds<crop_resize_tp_kernel<uint8_t, T>>(who, g, dim3(256), lds, s, q));
+}
+
+// the checks the two activation entries share; fills the output description
+static int32_t act_out_args(const char *who, int32_t T, int32_t H, int32_t W, int32_t C, int32_t n_clips, int32_t first, int32_t clip_step, int32_t frame_step,
+                            int32_t t_clip, int32_t y0, int32_t x0, int32_t ch, int32_t cw, int32_t oh, int32_t ow, void *act, int32_t cpad, int32_t dtype, ActOutKP *a) {
+    TS_REQUIRE(T > 0 && H > 0 && W > 0 && C > 0 && C <= 3 && oh > 0 && ow > 0, "%s: bad sizes (<= 3 channels)", who);
+    TS_REQUIRE(n_clips > 0 && t_clip > 0 && frame_step > 0 && clip_step >= 0 && first >= 0, "%s: bad clip sampling", who);
+    TS_REQUIRE(y0 >= 0 && x0 >= 0 && ch > 0 && cw > 0 && y0 + ch <= H && x0 + cw <= W, "%s: crop box (%d,%d,%d,%d) outside the %dx%d frame", who, y0, x0, ch, cw, H, W);
+    TS_REQUIRE(cpad == 4 || cpad == 8, "%s: cpad must be 4 (pixel pairs) or 8", who);
+    TS_REQUIRE(cpad == 8 || ow % 2 == 0, "%s: cpad=4 packs pixel pairs, the output width %d must be even", who, ow);
+    TS_REQUIRE(dtype == TEDSPAD_F16 || dtype == TEDSPAD_BF16, "%s: bad dtype", who);
+    TS_REQUIRE((uintptr_t)act % 16 == 0, "%s: the activation must be 16-byte aligned", who);
+    TS_REQUIRE((long)n_clips * t_clip * oh < (1L << 31), "%s: %d clips x %d frames x %d rows do not fit one launch", who, n_clips, t_clip, oh);
+    a->act = (uint4 *)act; a->first = first; a->clip_step = clip_step; a->frame_step = frame_step; a->t_clip = t_clip; a->cpad = cpad;
+    return TEDSPAD_OK;
+}
+
+extern "C" int32_t tedspad_frames_crop_resize_act(const void *frames, int32_t in_is_float, int32_t T, int32_t H, int32_t W, int32_t C, int32_t n_clips,
+                                                  int32_t first, int32_t clip_step, int32_t frame_step, int32_t t_clip, int32_t y0, int32_t x0, int32_t ch,
+                                                  int32_t cw, int32_t oh, int32_t ow, const int32_t *ytab, const int32_t *xtab, float divisor, int32_t flip,
+                                                  void *act, int32_t cpad, int32_t dtype, void *stream) {
+    const char *who = "tedspad_frames_crop_resize_act";
+    TS_REQUIRE(frames && act && ytab && xtab, "tedspad_frames_crop_resize_act: null pointer");
+    TS_REQUIRE(divisor != 0.f, "tedspad_frames_crop_resize_act: divisor must be non-zero");
+    ActOutKP a;
+    const int32_t rc = act_out_args(who, T, H, W, C, n_clips, first, clip_step, frame_step, t_clip, y0, x0, ch, cw, oh, ow, act, cpad, dtype, &a);
+    if (rc != TEDSPAD_OK) return rc;
+    const size_t lds = (size_t)ow * cpad * 2 + (size_t)cw * C * sizeof(float) + 1024;       // the 16-bit output row + the fp32 row buffer + the value table
+    TS_REQUIRE(lds <= 160 * 1024, "tedspad_frames_crop_resize_act: %d output columns + a %d x %d row buffer exceed the CU's 160 KB of LDS", ow, cw, C);
+    ResizeKP p;
+    p.in = frames; p.out = nullptr; p.ytab = ytab; p.xtab = xtab;
+    p.T = T; p.H = H; p.W = W; p.C = C; p.y0 = y0; p.x0 = x0; p.ch = ch; p.cw = cw; p.oh = oh; p.ow = ow;
+    p.ytaps = aa_taps(ch, oh); p.xtaps = aa_taps(cw, ow); p.flip = flip; p.div = divisor;
+    p.so_t = p.so_c = p.so_h = p.so_w = 0;
+    const uint8_t *in_end = (const uint8_t *)frames + (size_t)T * H * W * C * (in_is_float ? 4 : 1);
+    hipStream_t s = (hipStream_t)stream;
+    const dim3 g((unsigned)((long)n_clips * t_clip * oh));
+    if (in_is_float) TS_WITH_T(dtype, return launch_lds<crop_resize_act_kernel<float, T>>(who, g, dim3(256), lds, s, p, a, in_end));
+    TS_WITH_T(dtype, return launch_lds<crop_resize_act_kernel<uint8_t, T>>(who, g, dim3(256), lds, s, p, a, in_end));
+}
+
+extern "C" int32_t tedspad_frames_crop_resize_pil_act(const void *frames, int32_t T, int32_t H, int32_t W, int32_t C, int32_t n_clips, int32_t first,
+                                                      int32_t clip_step, int32_t frame_step, int32_t t_clip, int32_t y0, int32_t x0, int32_t ch, int32_t cw,
+                                                      int32_t oh, int32_t ow, const int32_t *ytab, int32_t ytaps, const int32_t *xtab, int32_t xtaps,
+                                                      void *act, int32_t cpad, int32_t dtype, void *stream) {
+    const char *who = "tedspad_frames_crop_resize_pil_act";
+    TS_REQUIRE(frames && act && ytab && xtab && ytaps > 0 && xtaps > 0, "tedspad_frames_crop_resize_pil_act: bad arguments");
+    ActOutKP a;
+    const int32_t rc = act_out_args(who, T, H, W, C, n_clips, first, clip_step, frame_step, t_clip, y0, x0, ch, cw, oh, ow, act, cpad, dtype, &a);
+    if (rc != TEDSPAD_OK) return rc;
+    const size_t lds = (size_t)ow * cpad * 2;
+    TS_REQUIRE(lds <= 160 * 1024, "tedspad_frames_crop_resize_pil_act: %d output columns exceed the CU's 160 KB of LDS", ow);
+    ResizeU8KP p;
+    p.in = (const uint8_t *)frames; p.out = nullptr; p.ytab = ytab; p.xtab = xtab;
+    p.T = T; p.H = H; p.W = W; p.C = C; p.y0 = y0; p.x0 = x0; p.oh = oh; p.ow = ow; p.ytaps = ytaps; p.xtaps = xtaps;
+    p.so_t = p.so_c = p.so_h = p.so_w = 0;
+    const dim3 g((unsigned)((long)n_clips * t_clip * oh));
+    TS_WITH_T(dtype, return launch_lds<crop_resize_pil_act_kernel<T>>(who, g, dim3(256), lds, (hipStream_t)stream, p, a));
 }
 
 extern "C" int32_t tedspad_segment_pool_mag(const float *feat, int32_t T, int32_t ncrops, int32_t F, int32_t length, float *out,

@@ -161,10 +161,12 @@ def require_cuda(t: torch.Tensor, what: str):
 @dataclass
 class Act:
     """A channels-last activation: `buf` is (n, t, h, w, ld) 16-bit; this view covers
-    channels [coff, coff + c) of every pixel (concat slices share one buffer)."""
+    channels [coff, coff + c) of every pixel (concat slices share one buffer). `cpad`: set on a network's INPUT activation only
+    (clip_to_act, preprocess.crop_resize_act): the channel count every pixel was padded to, 4 = the pixel-pair buffer; 0 anywhere else."""
     buf: torch.Tensor
     c: int
     coff: int = 0
+    cpad: int = 0
 
     @property
     def dims(self) -> Tuple[int, int, int, int]:
@@ -957,7 +959,7 @@ def clip_to_act(x: torch.Tensor, cpad: int, dtype: str = DEFAULT_DTYPE) -> Act:
     sn, sc, st, sh, sw = x.stride()
     check(_lib.lib().tedspad_clip_to_channels_last(x.data_ptr(), buf.data_ptr(), n, c, t, h, w, sn, sc, st, sh, sw,
                                                    cpad, code, _stream_ptr()), "tedspad_clip_to_channels_last")
-    return Act(buf, 8)
+    return Act(buf, 8, 0, cpad)
 
 
 class StemPT:

@@ -228,6 +228,112 @@ def extract_video_features_uint8(ft_model, frames: torch.Tensor, cropping_factor
     return out
 
 
+def anonymized_video_box(h: int, w: int, c: int = 3, cropping_factor: float = 0.8, no_ar_distortion: bool = False, resample: str = "aa"):
+    """The centre-crop box (y0, x0, ch, cw) the extraction scripts take from an (h, w, c) frame: resample 'aa' -> `val_augmentations`'
+    (dali_extraction.py:38-50: int(h * factor) x int(w * factor), or the square of the shorter side), 'pil' -> `shanghai_frames_dataset.augmentation`'s
+    (shanghai_dl.py:27-35 through preprocess.shanghai_crop_size, quirks included); both through torchvision's center_crop rule (preprocess.center_crop_box)."""
+    from . import preprocess
+    if resample == "aa":
+        if no_ar_distortion:
+            ch = cw = int(min(h, w) * cropping_factor)
+        else:
+            ch, cw = int(h * cropping_factor), int(w * cropping_factor)
+    elif resample == "pil":
+        ch, cw = preprocess.shanghai_crop_size(h, w, c, cropping_factor, no_ar_distortion)
+    else:
+        raise ValueError("resample must be 'aa' or 'pil', got %r" % (resample,))
+    if ch < 1 or cw < 1:
+        raise ValueError("empty crop %dx%d of a %dx%dx%d frame" % (ch, cw, h, w, c))
+    return preprocess.center_crop_box(h, w, ch, cw)
+
+
+def anonymized_video_clips(t: int, resample: str = "aa", first: int = 0, clip_step: int = 32, frame_step: int = 2, t_clip: int = 16) -> int:
+    """How many clips the extraction scripts cut from `t` decoded frames when clip i, frame f is source frame first + i*clip_step + f*frame_step:
+    'aa'  -> a clip for every start inside the video, ceil((t - first) / clip_step): HybridValPipe with pad_sequences (dali_extraction.py:62-73) pads the last
+             one with zero frames;
+    'pil' -> the clips ALL of whose frames exist: `read_video` (shanghai_dl.py:73-80) appends a clip only when its 16th frame arrived. With first = frame_step - 1
+             and clip_step = t_clip * frame_step (the script's frames: count % fix_skip == 0, counting from 1) that is t // (t_clip * frame_step)."""
+    if resample not in ("aa", "pil"):
+        raise ValueError("resample must be 'aa' or 'pil', got %r" % (resample,))
+    if clip_step < 1 or frame_step < 1 or t_clip < 1 or first < 0:
+        raise ValueError("bad clip sampling: first %d, clip_step %d, frame_step %d, t_clip %d" % (first, clip_step, frame_step, t_clip))
+    if resample == "aa":
+        return max(0, -(-(t - first) // clip_step))
+    last = first + (t_clip - 1) * frame_step              # clip 0's last frame
+    return 0 if last >= t else (t - 1 - last) // clip_step + 1
+
+
+@torch.no_grad()
+def extract_anonymized_video_features_uint8(ft_model, fa_model, frames: torch.Tensor, cropping_factor: float = 0.8, no_ar_distortion: bool = False,
+                                            out_hw=(224, 224), clip_step: int = 32, frame_step: int = 2, t_clip: int = 16, first: int = 0, n_clips: int = None,
+                                            batch: int = 75, fa_batch: int = 75, layout: str = "reference", resample: str = "aa", streams: int = 2,
+                                            out: torch.Tensor = None) -> torch.Tensor:
+    """The per-video path the reference's two extraction scripts really run (`anonymized = True` is hard-coded: dali_extraction.py:108,169-178,
+    st_feature_extraction.py:24-30), from DECODED FRAMES resident on the GPU: frames (T,H,W,3) uint8 (resample 'aa': or the float frames DALI hands over) ->
+    clip sampling (clip i, frame f = source frame first + i*clip_step + f*frame_step) -> per frame / 255, centre crop, resize -> fa on every frame -> the Q1
+    reshape (layout 'reference') or the permute (layout 'permute') of `feed` -> ft.extract_features -> (n_clips, F) fp32 rows on the GPU.
+
+    resample 'aa' is dali_extraction.py: `val_augmentations`' box and antialiased resize; n_clips=None -> a clip per `clip_step` source frames, frames past the
+    end are zero frames (pad_sequences) -- which go through fa like any other frame, as in the reference (fa of a black frame is not black).
+    resample 'pil' is st_feature_extraction.py's loader (shanghai_dl.py): `augmentation`'s box and Pillow resize, uint8 frames; n_clips=None -> whole clips only.
+    `read_video`'s frames are first = frame_step - 1, clip_step = t_clip * frame_step (and frame_step = 1 for videos shorter than 32 frames). Its `repeat`
+    branch for videos shorter than 16 frames (the last frame stacked until the clip is full) stays with the caller: repeat the frame in `frames`.
+
+    Per `fa_batch` clips ONE launch (preprocess.crop_resize_act) writes the 16-bit channels-last activation fa's first conv reads and `fa_model.forward_act`
+    starts from it: no fp32 frame batch is written or read back, and the rows are bit-identical to `extract_anonymized_clip_features` on the fp32 clips.
+    `batch` clips per encoder forward, the batches alternating over `streams` HIP streams. `fa_model`: UnetPlusPlus or UNet."""
+    from . import engine as E, preprocess
+    if not hasattr(fa_model, "forward_act"):
+        raise TypeError("extract_anonymized_video_features_uint8: fa_model %s has no forward_act (UnetPlusPlus and UNet start from the 16-bit activation)"
+                        % type(fa_model).__name__)
+    if layout not in ("reference", "permute"):
+        raise ValueError("extract_anonymized_video_features_uint8: layout must be 'reference' or 'permute', got %r" % (layout,))
+    E.require_cuda(frames, "extract_anonymized_video_features_uint8")
+    if frames.dim() != 4:
+        raise ValueError("extract_anonymized_video_features_uint8: frames must be (T,H,W,C), got %s" % (tuple(frames.shape),))
+    fx = _extract_fn(ft_model)
+    t, h, w, c = frames.shape
+    box = anonymized_video_box(h, w, c, cropping_factor, no_ar_distortion, resample)
+    if n_clips is None:
+        n_clips = anonymized_video_clips(t, resample, first, clip_step, frame_step, t_clip)
+    oh, ow = int(out_hw[0]), int(out_hw[1])
+    dev = frames.device
+    if out is None:
+        out = torch.empty((n_clips, feature_width(ft_model)), dtype=torch.float32, device=dev)
+    if tuple(out.shape) != (n_clips, feature_width(ft_model)) or out.dtype != torch.float32 or out.device != dev:
+        raise ValueError("extract_anonymized_video_features_uint8: out must be fp32 (%d, %d) on %s" % (n_clips, feature_width(ft_model), dev))
+    if n_clips == 0:
+        return out
+    cpad, dt = fa_model.ACT_CPAD, fa_model.compute_dtype
+    fa_step = fa_batch if fa_batch else batch
+
+    def anonymized(i, k):       # clips i .. i + k - 1 -> fa's output frames (k * t_clip, c, oh, ow) fp32
+        act = preprocess.crop_resize_act(frames, box, (oh, ow), k, first=first + i * clip_step, clip_step=clip_step, frame_step=frame_step, t_clip=t_clip,
+                                         cpad=cpad, dtype=dt, resample=resample)
+        return fa_model.forward_act(act)
+
+    pool = _STREAMS.setdefault((dev, streams), [torch.cuda.Stream(device=dev) for _ in range(max(1, streams))])
+    main = torch.cuda.current_stream(dev)
+    for st in pool:
+        st.wait_stream(main)
+    for j, i in enumerate(range(0, n_clips, batch)):
+        b = min(batch, n_clips - i)
+        with torch.cuda.stream(pool[0 if E.tuning_pending() else j % len(pool)]):
+            if b > fa_step:
+                fr = torch.empty((b * t_clip, c, oh, ow), dtype=torch.float32, device=dev)
+                for q in range(0, b, fa_step):
+                    k = min(fa_step, b - q)
+                    fr[q * t_clip:(q + k) * t_clip] = anonymized(i + q, k)
+            else:
+                fr = anonymized(i, b)
+            x = fr.reshape(b, c, t_clip, oh, ow) if layout == "reference" else fr.reshape(b, t_clip, c, oh, ow).permute(0, 2, 1, 3, 4)
+            out[i:i + b] = fx(x).flatten(1)
+    for st in pool:
+        main.wait_stream(st)
+    warn_if_saturated(ft_model)
+    return out
+
+
 def share_tile_choices(ft_model, group=None, src: int = 0) -> int:
     """Multi-GPU jobs: broadcast rank `src`'s decided conv tile configurations (engine.export_tile_table of the packed network) to every rank, so that all
     ranks run the same tiles -- identical clips then give bit-identical features on every GPU and no rank spends its first forwards tuning. Call it once

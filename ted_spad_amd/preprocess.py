@@ -24,7 +24,7 @@ import torch
 
 from . import _lib
 from ._lib import check
-from .engine import _stream_ptr, require_cuda
+from .engine import DEFAULT_DTYPE, DTYPES, Act, _stream_ptr, require_cuda
 
 _TABLES = {}
 
@@ -205,6 +205,54 @@ def crop_resize_pil(frames: torch.Tensor, box, out_hw, out: torch.Tensor = None,
     check(_lib.lib().tedspad_frames_crop_resize_pil(frames.data_ptr(), t, h, w, c, y0, x0, ch, cw, oh, ow, ytab.data_ptr(), ky, xtab.data_ptr(), kx,
                                                     out.data_ptr(), so[0], so[1], s[2], s[3], _stream_ptr()), "tedspad_frames_crop_resize_pil")
     return out
+
+
+def crop_resize_act(frames: torch.Tensor, box, out_hw, n_clips: int, first: int = 0, clip_step: int = 32, frame_step: int = 2, t_clip: int = 16,
+                    cpad: int = 4, dtype: str = DEFAULT_DTYPE, flip: bool = False, resample: str = "aa", divisor: float = 255.0, out: torch.Tensor = None) -> Act:
+    """frames: (T,H,W,C<=3) decoder frames on the GPU -> the ANONYMIZER's input activation of `n_clips` clips in ONE launch: clip i, frame f = source frame
+    first + i*clip_step + f*frame_step (an index >= T is a zero frame), each frame / divisor -> crop `box` -> resize to `out_hw` (-> flip), stored as frame
+    i*t_clip + f of the 16-bit channels-last Act that `engine.clip_to_act(x.unsqueeze(2), cpad, dtype)` builds from the fp32 frames x (n_clips*t_clip, C, oh, ow):
+    cpad=4 -> the pixel-pair buffer (frames, 1, oh, ow/2, 8) UnetPlusPlus takes, cpad=8 -> (frames, 1, oh, ow, 8) as UNet takes it; bit-identical to it, and the
+    fp32 frames are never written. resample 'aa': `crop_resize`'s arithmetic (uint8 or float32 frames); 'pil': `crop_resize_pil`'s (uint8 frames, divisor 255,
+    no flip). `out`: a contiguous 16-bit buffer of that shape to fill. Feed the result to `UnetPlusPlus.forward_act` / `UNet.forward_act`."""
+    require_cuda(frames, "crop_resize_act")
+    if resample not in ("aa", "pil"):
+        raise ValueError("crop_resize_act: resample must be 'aa' or 'pil', got %r" % (resample,))
+    ok = (torch.uint8, torch.float32) if resample == "aa" else (torch.uint8,)
+    if frames.dim() != 4 or frames.dtype not in ok or not frames.is_contiguous():
+        raise ValueError("crop_resize_act: frames must be a contiguous (T,H,W,C) %s tensor" % ("uint8/float32" if resample == "aa" else "uint8 (PIL images are 8-bit)"))
+    if resample == "pil" and (flip or float(divisor) != 255.0):
+        raise ValueError("crop_resize_act: resample='pil' is to_tensor's / 255 without a flip (crop_resize_pil)")
+    if cpad not in (4, 8):
+        raise ValueError("crop_resize_act: cpad must be 4 (pixel pairs) or 8")
+    t, h, w, c = frames.shape
+    y0, x0, ch, cw = [int(v) for v in box]
+    oh, ow = int(out_hw[0]), int(out_hw[1])
+    if cpad == 4 and ow % 2:
+        raise ValueError("crop_resize_act: cpad=4 packs pixel pairs, the output width %d must be even" % ow)
+    n_clips, t_clip = int(n_clips), int(t_clip)
+    tdt, code = DTYPES[dtype]
+    shape = (n_clips * t_clip, 1, oh, ow // 2 if cpad == 4 else ow, 8)
+    if out is None:
+        out = torch.empty(shape, dtype=tdt, device=frames.device)
+    if tuple(out.shape) != shape or out.dtype != tdt or not out.is_contiguous() or out.device != frames.device:
+        raise ValueError("crop_resize_act: out must be a contiguous %s tensor of %s on %s" % (shape, tdt, frames.device))
+    row16 = 2 * ow * cpad                                              # bytes of one output row
+    step = max(1, ((1 << 31) - 1) // (t_clip * oh))                   # clips per launch: the kernels number (frame, row) workgroups in 32 bits
+    for i0 in range(0, n_clips, step):
+        k = min(step, n_clips - i0)
+        dst = out.data_ptr() + i0 * t_clip * oh * row16
+        if resample == "aa":
+            ytab, xtab = _table(ch, oh, frames.device), _table(cw, ow, frames.device)
+            check(_lib.lib().tedspad_frames_crop_resize_act(frames.data_ptr(), int(frames.dtype == torch.float32), t, h, w, c, k, int(first) + i0 * int(clip_step),
+                                                            int(clip_step), int(frame_step), t_clip, y0, x0, ch, cw, oh, ow, ytab.data_ptr(), xtab.data_ptr(),
+                                                            C.c_float(divisor), int(flip), dst, cpad, code, _stream_ptr()), "tedspad_frames_crop_resize_act")
+        else:
+            (ytab, ky), (xtab, kx) = _pil_table(ch, oh, frames.device), _pil_table(cw, ow, frames.device)
+            check(_lib.lib().tedspad_frames_crop_resize_pil_act(frames.data_ptr(), t, h, w, c, k, int(first) + i0 * int(clip_step), int(clip_step), int(frame_step),
+                                                                t_clip, y0, x0, ch, cw, oh, ow, ytab.data_ptr(), ky, xtab.data_ptr(), kx, dst, cpad, code,
+                                                                _stream_ptr()), "tedspad_frames_crop_resize_pil_act")
+    return Act(out, 8, 0, cpad)
 
 
 def shanghai_crop_size(h: int, w: int, c: int, cropping_factor: float = 0.8, no_ar_distortion: bool = False):

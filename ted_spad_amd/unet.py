@@ -49,6 +49,8 @@ class OutConv(nn.Module):
 
 
 class UNet(nn.Module):
+    ACT_CPAD = 8           # forward_act's input layout: clip_to_act(..., cpad=8)
+
     def __init__(self, n_channels, n_classes, bilinear=True, dtype=E.DEFAULT_DTYPE):
         super().__init__()
         if not bilinear:
@@ -109,10 +111,26 @@ class UNet(nn.Module):
         E.require_cuda(x, "UNet")
         if x.dim() != 4 or x.shape[1] != self.n_channels:
             raise ValueError("expected (N,%d,H,W), got %s" % (self.n_channels, tuple(x.shape)))
-        P = self.packed()
-        n, _, H, W = x.shape
+        return self.forward_act(E.clip_to_act(x.unsqueeze(2), cpad=8, dtype=self.compute_dtype), taps)     # (N,1,H,W,8)
+
+    def forward_act(self, a: E.Act, taps=None) -> torch.Tensor:
+        """The eval forward from the input ACTIVATION: the buffer (N, 1, H, W, 8) of this network's storage type, channels >= n_channels zero, that
+        `engine.clip_to_act(x.unsqueeze(2), cpad=8, dtype=self.compute_dtype)` builds from the fp32 frames x (N,n_channels,H,W) -- `forward(x)` is exactly that call
+        followed by this one -- or that `preprocess.crop_resize_act(..., cpad=8)` writes straight from decoded frames. Returns (N,n_classes,H,W) fp32."""
+        if self.training:
+            raise RuntimeError("UNet.forward_act is the eval forward: call eval() first (train() runs forward(x) through the autograd path)")
         tdt = E.DTYPES[self.compute_dtype][0]
-        a = E.clip_to_act(x.unsqueeze(2), cpad=8, dtype=self.compute_dtype)     # (N,1,H,W,8)
+        if not isinstance(a, E.Act) or a.buf.dim() != 5:
+            raise TypeError("UNet.forward_act: expected an engine.Act (N,1,H,W,8), as clip_to_act(x.unsqueeze(2), cpad=8) returns it")
+        E.require_cuda(a.buf, "UNet")
+        if a.buf.dtype != tdt:
+            raise ValueError("UNet.forward_act: the activation is %s, compute_dtype %r stores %s" % (a.buf.dtype, self.compute_dtype, tdt))
+        if a.cpad != self.ACT_CPAD or a.c != 8 or a.ld != 8 or a.coff != 0 or a.dims[1] != 1 or not a.buf.is_contiguous():
+            raise ValueError("UNet.forward_act: expected the contiguous layout (N,1,H,W,8) (cpad=8: one pixel x 8 channels), got %s with %d channels, cpad %d"
+                             % (tuple(a.buf.shape), a.c, a.cpad))
+        P = self.packed()
+        n, _, H, W = a.dims
+        dev = a.buf.device
         pad = (0, 1, 1)
         # encoder: level i output (channels enc[i]) goes to the left slice of decoder concat buffer cat[i]
         enc_c = (64, 128, 256, 512)
@@ -124,7 +142,7 @@ class UNet(nn.Module):
             if lvl > 0:
                 cur = E.maxpool(cur, (1, 2, 2), (1, 2, 2))
                 h, w = h // 2, w // 2
-            cat = E.Act.empty(n, 1, h, w, 2 * enc_c[lvl], tdt, x.device)
+            cat = E.Act.empty(n, 1, h, w, 2 * enc_c[lvl], tdt, dev)
             mid = pcs[0](cur, pads=pad)
             skip = pcs[1](mid, pads=pad, out=cat.slice(0, enc_c[lvl]))
             cats.append(cat)

@@ -103,6 +103,8 @@ class UnetPlusPlusDecoder(nn.Module):
 
 
 class UnetPlusPlus(nn.Module):
+    ACT_CPAD = 4           # forward_act's input layout: clip_to_act(..., cpad=4), pixel pairs (the stem's pair_w form)
+
     def __init__(self, dtype=E.DEFAULT_DTYPE):
         super().__init__()
         self.encoder = ResNet18Encoder()
@@ -199,11 +201,10 @@ class UnetPlusPlus(nn.Module):
         assert out.dims == x.dims and out.c == x.c
         check(_lib.lib().tedspad_copy_channels(x.ptr, out.ptr, n * h * w, x.c, x.ld, out.ld, _stream_ptr()), "tedspad_copy_channels")
 
-    def _forward_gathered(self, x: torch.Tensor, P, taps=None) -> torch.Tensor:
+    def _forward_gathered(self, a: Act, P, taps=None) -> torch.Tensor:
         """The eval forward with every decoder block's `interpolate(x, 2, 'nearest')` + `torch.cat([x, *skips])` read IN PLACE by its first conv
         (PackedConv.gather: per-64-channel-chunk sources, half-resolution ones through the x2 index map): no upsampled tensor, no concat buffer, no copies."""
         pad = (0, 1, 1)
-        a = E.clip_to_act(x.unsqueeze(2), cpad=4, dtype=self.compute_dtype)
         st = P["stem"]
         f1 = st(a, pads=(0, 3, st.pair_pw), pads_back=(0, 3, st.k[2] - 1 - st.pair_pw))
         cur = E.maxpool(f1, (1, 3, 3), (1, 2, 2), pads=(0, 1, 1))
@@ -246,21 +247,40 @@ class UnetPlusPlus(nn.Module):
         n, _, H, W = x.shape
         if H % 16 or W % 16:       # smp.base.model.SegmentationModel.check_input_shape (output stride 2**depth)
             raise RuntimeError("Wrong input shape height=%d, width=%d. Expected image height and width divisible by 16." % (H, W))
-        P = self.packed()
+        return self.forward_act(E.clip_to_act(x.unsqueeze(2), cpad=4, dtype=self.compute_dtype), taps)
+
+    def forward_act(self, a: Act, taps=None) -> torch.Tensor:
+        """The eval forward from the input ACTIVATION: the pixel-pair buffer (N, 1, H, W/2, 8) of this network's storage type that
+        `engine.clip_to_act(x.unsqueeze(2), cpad=4, dtype=self.compute_dtype)` builds from the fp32 frames x (N,3,H,W) -- `forward(x)` is exactly that call followed
+        by this one -- or that `preprocess.crop_resize_act(..., cpad=4)` writes straight from decoded frames. Returns (N,3,H,W) fp32."""
+        if self.training:
+            raise RuntimeError("UnetPlusPlus.forward_act is the eval forward: call eval() first (train() runs forward(x) through the autograd path)")
         tdt = E.DTYPES[self.compute_dtype][0]
-        dev = x.device
+        if not isinstance(a, Act) or a.buf.dim() != 5:
+            raise TypeError("UnetPlusPlus.forward_act: expected an engine.Act (N,1,H,W/2,8), as clip_to_act(x.unsqueeze(2), cpad=4) returns it")
+        E.require_cuda(a.buf, "UnetPlusPlus")
+        if a.buf.dtype != tdt:
+            raise ValueError("UnetPlusPlus.forward_act: the activation is %s, compute_dtype %r stores %s" % (a.buf.dtype, self.compute_dtype, tdt))
+        if a.cpad != self.ACT_CPAD or a.c != 8 or a.ld != 8 or a.coff != 0 or a.dims[1] != 1 or not a.buf.is_contiguous():
+            raise ValueError("UnetPlusPlus.forward_act: expected the contiguous pixel-pair layout (N,1,H,W/2,8) (cpad=4: two pixels x {c0,c1,c2,0}), got %s with %d channels, cpad %d"
+                             % (tuple(a.buf.shape), a.c, a.cpad))
+        n, _, H, W = a.dims
+        W *= 2
+        if H % 16 or W % 16:       # smp.base.model.SegmentationModel.check_input_shape (output stride 2**depth)
+            raise RuntimeError("Wrong input shape height=%d, width=%d. Expected image height and width divisible by 16." % (H, W))
+        P = self.packed()
+        dev = a.buf.device
 
         def buf(c, div):
             return Act.empty(n, 1, H // div, W // div, c, tdt, dev)
 
         pad = (0, 1, 1)
         if E.GATHER_CAT:
-            return self._forward_gathered(x, P, taps)
+            return self._forward_gathered(a, P, taps)
         # concat buffers (leading slice = the upsampled input of the block, then the skips in smp's torch.cat order)
         B00, B11, B22 = buf(384, 8), buf(192, 4), buf(128, 2)      # [up(f4)|f3]  [up(f3)|f2]  [up(f2)|f1]
         B01, B12, B02 = buf(384, 4), buf(192, 2), buf(320, 2)      # [up(x00)|x11|f2]  [up(x11)|x22|f1]  [up(x01)|x12|x22|f1]
         # ---- encoder (smp ResNetEncoder.forward: conv1+bn1+relu | maxpool+layer1 | layer2 | layer3) ----
-        a = E.clip_to_act(x.unsqueeze(2), cpad=4, dtype=self.compute_dtype)
         st = P["stem"]
         f1 = st(a, pads=(0, 3, st.pair_pw), pads_back=(0, 3, st.k[2] - 1 - st.pair_pw), out=B22.slice(64, 64))
         cur = E.maxpool(f1, (1, 3, 3), (1, 2, 2), pads=(0, 1, 1))
