@@ -653,14 +653,16 @@ int32_t tedspad_mgfn_gemm(const float *x, int32_t ldx, const int32_t *bounds, in
                           const float *bias, int32_t gelu, const float *res, int32_t ldres, float *y, int32_t ldy, int32_t M, int32_t N,
                           void *stream);
 /* GLANCE attention: qkv rows = q | k | v, each heads x 64 channels (head-blocked, 'b (h d) n'); out[m, h * 64 + d] =
- * softmax_j((q_m / 8) . k_j) v_j over m's sequence. tmax >= the longest sequence. */
+ * softmax_j((q_m / 8) . k_j) v_j over m's sequence. tmax >= the longest sequence; heads and (tmax + 31) / 32 at most 65535 (as
+ * tedspad_mgfn_attention_bwd). */
 int32_t tedspad_mgfn_attention(const float *qkv, int32_t ldqkv, const int32_t *seq_off, int32_t nseq, int32_t tmax, int32_t heads, float *out,
                                int32_t ldo, void *stream);
 /* FOCUS rel_pos: out[m, c] = b[c % heads] + sum_t w[c % heads, t] v[m + t - 2, c] (5 taps, zero outside the sequence; head-interleaved
- * channels). C, ldv, ldo % 4 == 0, out != v. */
+ * channels). C, ldv, ldo % 4 == 0, ldv, ldo >= C, out != v. */
 int32_t tedspad_mgfn_relpos(const float *v, int32_t ldv, const int32_t *bounds, int32_t M, int32_t C, int32_t heads, const float *w,
                             const float *b, float *out, int32_t ldo, void *stream);
-/* h = nn.LayerNorm(C)(x) (written when h != NULL, (M, C)), logit = h . fc_w + fc_b, score = sigmoid(logit), mag = ||h||_2, each (M). */
+/* h = nn.LayerNorm(C)(x) (written when h != NULL, (M, C)), logit = h . fc_w + fc_b, score = sigmoid(logit), mag = ||h||_2, each (M).
+ * C, ldx % 4 == 0, ldx >= C. */
 int32_t tedspad_mgfn_head(const float *x, int32_t ldx, int32_t M, int32_t C, const float *ln_w, const float *ln_b, const float *fc_w, float fc_b,
                           float eps, float *h, float *logit, float *score, float *mag, void *stream);
 /* Crop means: video v owns segments seg_off[v] .. seg_off[v+1] (T_v of them) and tokens ncrops * seg_off[v] + c * T_v + t;

@@ -374,7 +374,8 @@ extern "C" int32_t tedspad_mgfn_gemm(const float *x, int32_t ldx, const int32_t 
 
 extern "C" int32_t tedspad_mgfn_attention(const float *qkv, int32_t ldqkv, const int32_t *seq_off, int32_t nseq, int32_t tmax, int32_t heads,
                                           float *out, int32_t ldo, void *stream) {
-    TS_REQUIRE(qkv && seq_off && out && nseq > 0 && tmax > 0 && heads > 0, "tedspad_mgfn_attention: bad arguments");
+    TS_REQUIRE(qkv && seq_off && out && nseq > 0 && tmax > 0 && heads > 0 && heads <= 65535 && (tmax + 31) / 32 <= 65535,
+               "tedspad_mgfn_attention: bad arguments (heads and tmax / 32 at most 65535: the grid's y and z)");
     TS_REQUIRE(ldqkv % 4 == 0 && ldqkv >= 3 * heads * AT_D && ldo >= heads * AT_D && al16(qkv),
                "tedspad_mgfn_attention: qkv rows must hold q | k | v (3 x heads x %d), 16-byte aligned", AT_D);
     hipLaunchKernelGGL(attention_kernel, dim3(nseq, (tmax + 31) / 32, heads), dim3(64), 0, (hipStream_t)stream, qkv, ldqkv, seq_off, heads,
@@ -384,9 +385,9 @@ extern "C" int32_t tedspad_mgfn_attention(const float *qkv, int32_t ldqkv, const
 
 extern "C" int32_t tedspad_mgfn_relpos(const float *v, int32_t ldv, const int32_t *bounds, int32_t M, int32_t C, int32_t heads, const float *w,
                                        const float *b, float *out, int32_t ldo, void *stream) {
-    TS_REQUIRE(v && bounds && w && b && out && M > 0 && heads > 0 && C % 4 == 0 && ldv % 4 == 0 && ldo % 4 == 0 && al16(v) && al16(out) &&
-                   v != out,
-               "tedspad_mgfn_relpos: bad arguments (C, ldv, ldo %% 4 == 0, 16-byte aligned, not in place)");
+    TS_REQUIRE(v && bounds && w && b && out && M > 0 && heads > 0 && C > 0 && C % 4 == 0 && ldv % 4 == 0 && ldo % 4 == 0 && ldv >= C &&
+                   ldo >= C && al16(v) && al16(out) && v != out,
+               "tedspad_mgfn_relpos: bad arguments (C, ldv, ldo %% 4 == 0, ldv, ldo >= C, 16-byte aligned, not in place)");
     const long long n = (long long)M * (C / 4);
     hipLaunchKernelGGL(relpos_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, v, ldv, bounds, M, C, heads, w, b,
                        out, ldo);
@@ -395,9 +396,9 @@ extern "C" int32_t tedspad_mgfn_relpos(const float *v, int32_t ldv, const int32_
 
 extern "C" int32_t tedspad_mgfn_head(const float *x, int32_t ldx, int32_t M, int32_t C, const float *ln_w, const float *ln_b, const float *fc_w,
                                      float fc_b, float eps, float *h, float *logit, float *score, float *mag, void *stream) {
-    TS_REQUIRE(x && ln_w && ln_b && fc_w && logit && score && mag && M > 0 && C > 0 && C % 4 == 0 && ldx % 4 == 0 && al16(x) &&
+    TS_REQUIRE(x && ln_w && ln_b && fc_w && logit && score && mag && M > 0 && C > 0 && C % 4 == 0 && ldx % 4 == 0 && ldx >= C && al16(x) &&
                    al16(ln_w) && al16(ln_b) && al16(fc_w) && (!h || al16(h)),
-               "tedspad_mgfn_head: bad arguments (C, ldx %% 4 == 0, 16-byte aligned)");
+               "tedspad_mgfn_head: bad arguments (C, ldx %% 4 == 0, ldx >= C, 16-byte aligned)");
     const int per = LN_THREADS / 64;
     hipLaunchKernelGGL(head_kernel, dim3((M + per - 1) / per), dim3(LN_THREADS), 0, (hipStream_t)stream, x, ldx, M, C, ln_w, ln_b, fc_w, fc_b,
                        eps, h, logit, score, mag);

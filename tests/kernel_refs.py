@@ -3,7 +3,8 @@ and the two value generators their tests use; then the exact-arithmetic conv ref
 references, input conditions and case tables of the fused forward kernels (tests/test_hip_fused_exact.py), then the case table of the plain forward conv and the launcher's
 acceptance rule per tile configuration (fwd_accepts; tests/test_hip_conv_fwd_exact.py), then the inference max-pool reference, its launcher's selection restated
 (maxpool_form) and the pool / clip-layout case tables of tests/test_hip_infer_pool.py, and last the weight-image, BatchNorm-fold and gradient-unpack references (numpy) and
-case table of tests/test_hip_pack_exact.py. A plain helper module: tests/test_kernel_refs.py checks every reference here against float64 torch (autograd) on
+case table of tests/test_hip_pack_exact.py; at the very end the MGFN kernels' references with their per-element bounds (tests/test_hip_mgfn_edges.py) and the torch
+restatements the older MGFN kernel tests share. A plain helper module: tests/test_kernel_refs.py checks every reference here against float64 torch (autograd) on
 the CPU, the -m gpu op tests (test_hip_train_kernels.py, test_hip_head_ops.py, test_hip_losses.py) compare the kernels with them.
 
 Activations are channels-last: (pixels, C) for the BatchNorm kernels, (n, t, h, w, c) for the pools, (n, h, w, c) for the resizes. Everything returned is a
@@ -1689,3 +1690,546 @@ def fold_shift_bound(ref_shift, beta, mean, scale64, conv_bias=None):
     if conv_bias is not None:
         mag = mag + np.abs(np.asarray(conv_bias, np.float64) * scale64)
     return 0.5 * ulp32(ref_shift) + 4 * 2.0 ** -52 * mag
+
+
+# ---- MGFN kernels (csrc/mgfn.hip, csrc/mgfn_train.hip): float64 references, each with a per-element bound ---------------------------------------------
+# Every reference returns (value, bound) -- or a dict of such pairs -- as float64 tensors. A bound is built as tests/test_hip_head_ops.py builds its own:
+# (terms in the sum + a small constant) * 2^-24 * sum |terms| of that element, propagated to first order (and rounded up) through the few operations
+# around the sum. The order of an MFMA or butterfly sum is the kernel's business: (n + c) * 2^-24 * sum |terms| holds for ANY order of n terms. The
+# reductions over tokens have a chain of MT_CHUNK in-chunk terms plus the number of chunks (chain_tokens), the row kernels one of ceil(C / 256) float4
+# loads per lane plus a 6-step butterfly (chain_row). Where a kernel is handed fp32 statistics (ln_apply, ln_bwd, bn_bwd, col_reduce, head_bwd), so is its
+# reference: the bound then covers that kernel's own roundings only. expf / erff / logf / sqrtf: K_* * 2^-24 relative, K_* = 10x the worst per-element
+# ratio of torch's fp32 CPU result against float64 on the same inputs (measured: exp 1.04, erf 1.05, log 1.03, sqrt 1.07 -- test_kernel_refs.py
+# test_mgfn_transcendental_constants measures them again). FLOOR32, the smallest normal fp32, is added to every bound: a result below it may be flushed.
+U = F32_EPS
+K_EXP = K_ERF = K_LOG = K_SQRT = 11.0
+FLOOR32 = 2.0 ** -126
+MT_CHUNK = 128
+SQRT1_2, INV_SQRT_2PI, TWO_OVER_SQRT_PI = 0.5 ** 0.5, 1.0 / (2.0 * np.pi) ** 0.5, 2.0 / np.pi ** 0.5
+
+
+def f32(v):
+    """a float kernel argument as the kernel receives it"""
+    return float(np.float32(v))
+
+
+def chain_tokens(M):
+    return MT_CHUNK + (M + MT_CHUNK - 1) // MT_CHUNK
+
+
+def chain_row(C):
+    return 4 * ((C + 255) // 256) + 6
+
+
+def mgfn_ragged(lengths):
+    """sequence offsets (list, nseq + 1) and bounds (M, 2) int64: first / one-past-last token of each token's sequence."""
+    L = torch.tensor(list(lengths), dtype=torch.int64)
+    off = torch.zeros(len(L) + 1, dtype=torch.int64)
+    off[1:] = torch.cumsum(L, 0)
+    st = off[:-1].repeat_interleave(L)
+    return off.tolist(), torch.stack([st, st + L.repeat_interleave(L)], 1)
+
+
+# The torch restatements the two older MGFN test files (test_hip_mgfn.py, test_hip_mgfn_train_kernels.py) compare with, in the dtype they are handed; the
+# references below are held to them in float64 (test_kernel_refs.py).
+def mgfn_seqs(x, off):
+    return [x[off[i]:off[i + 1]] for i in range(len(off) - 1)]
+
+
+def mgfn_conv_seq(x, w, b, taps):
+    """x (T, cin) one sequence, w (N, taps, cin) -> Conv1d(padding = taps // 2) over time"""
+    return F.conv1d(x.t().unsqueeze(0), w.permute(0, 2, 1), b, padding=taps // 2)[0].t()
+
+
+def mgfn_conv_tokens(x, off, w, b, taps):
+    return torch.cat([mgfn_conv_seq(s, w, b, taps) for s in mgfn_seqs(x, off)])
+
+
+def mgfn_conv_autograd(x, w, b, taps, off, dy):
+    """(dx, dw, db) of sum(conv(x) * dy) by autograd in x's dtype."""
+    x, w, b = x.clone().requires_grad_(True), w.clone().requires_grad_(True), b.clone().requires_grad_(True)
+    (mgfn_conv_tokens(x, off, w, b, taps) * dy).sum().backward()
+    return x.grad, w.grad, b.grad
+
+
+def mgfn_attention_torch(qkv, off, heads, dt=D, do=None):
+    """softmax attention per sequence and head (qkv rows = q | k | v, each heads x 64) in dtype dt; with do: (out, d qkv) by autograd."""
+    x = qkv.to(dt).clone().requires_grad_(do is not None)
+    inner, outs = 64 * heads, []
+    for s in mgfn_seqs(x, off):
+        T = s.shape[0]
+        q, k, v = (t.reshape(T, heads, 64).transpose(0, 1) for t in s.chunk(3, dim=1))
+        outs.append((torch.softmax((q * 0.125) @ k.transpose(1, 2), -1) @ v).transpose(0, 1).reshape(T, inner))
+    out = torch.cat(outs)
+    if do is None:
+        return out.detach()
+    (out * do.to(dt)).sum().backward()
+    return out.detach(), x.grad
+
+
+def mgfn_relpos_torch(v, w, b, off, heads, dt=D, do=None):
+    """FOCUS rel_pos (utils.py:144-146: 'b (c h) t -> (b c) h t' gives channel ch the filter of head ch % heads) as a grouped Conv1d per sequence in dtype dt;
+    with do: (out, dv, dw, db) by autograd."""
+    C = v.shape[1]
+    vd, wd, bd = (t.to(dt).clone().requires_grad_(do is not None) for t in (v, w, b))
+    wf, bf = wd.repeat(C // heads, 1).unsqueeze(1), bd.repeat(C // heads)
+    y = torch.cat([F.conv1d(s.t().unsqueeze(0), wf, bf, padding=2, groups=C)[0].t() for s in mgfn_seqs(vd, off)])
+    if do is None:
+        return y.detach()
+    (y * do.to(dt)).sum().backward()
+    return y.detach(), vd.grad, wd.grad, bd.grad
+
+
+def mgfn_window(x, bounds, taps, wrong=None):
+    """(M, taps, C): A[m, t] = x[m + t - taps // 2] inside m's sequence, else 0 (bounds None: every token its own sequence). wrong = 'leak': a tap stops at
+    the ends of the batch only; 'reversed': tap t reads m - t + taps // 2."""
+    x = x.to(D)
+    M = x.shape[0]
+    m = torch.arange(M)
+    lo, hi = (m, m + 1) if bounds is None else (bounds[:, 0].long(), bounds[:, 1].long())
+    A = torch.zeros((M, taps, x.shape[1]), dtype=D)
+    for t in range(taps):
+        src = m + t - taps // 2
+        ok = (src >= 0) & (src < M) if wrong == "leak" else (src >= lo) & (src < hi)
+        A[ok, taps - 1 - t if wrong == "reversed" else t] = x[src[ok]]
+    return A
+
+
+def mgfn_gelu_ref(v):
+    """y = v Phi(v) = 0.5 v (1 + erf(v / sqrt 2)). Bound: the argument v / sqrt 2 carries 2 roundings (the constant, the product): erf moves by at most
+    erf'(a) |a| 2u; erff itself K_ERF u |erf|; 1 + erf one rounding; the two products one each (0.5 v is exact)."""
+    v = v.to(D)
+    a = v * SQRT1_2
+    e = torch.erf(a)
+    y = 0.5 * v * (1.0 + e)
+    de = TWO_OVER_SQRT_PI * torch.exp(-a * a) * a.abs() * 2 * U + K_ERF * U * e.abs() + U * (1.0 + e).abs()
+    return y, 0.5 * v.abs() * de + 2 * U * y.abs() + FLOOR32
+
+
+def mgfn_gelu_bwd_ref(v, dy):
+    """dx = dy (Phi(v) + v phi(v)), phi(v) = exp(-v^2 / 2) / sqrt(2 pi). Bound: Phi as in mgfn_gelu_ref; the argument of expf carries 2 roundings
+    (|arg| 2u relative in the result), expf K_EXP u, three products; the sum and the product with dy one rounding each."""
+    v, dy = v.to(D), dy.to(D)
+    a = v * SQRT1_2
+    e = torch.erf(a)
+    Phi = 0.5 * (1.0 + e)
+    dPhi = 0.5 * (TWO_OVER_SQRT_PI * torch.exp(-a * a) * a.abs() * 2 * U + K_ERF * U * e.abs() + U * (1.0 + e).abs()) + U * Phi
+    t = v * INV_SQRT_2PI * torch.exp(-0.5 * v * v)
+    dt = t.abs() * (K_EXP * U + v * v * U + 3 * U)
+    dx = dy * (Phi + t)
+    return dx, dy.abs() * (dPhi + dt + U * (Phi + t).abs()) + U * dx.abs() + FLOOR32
+
+
+def mgfn_gemm_ref(x, bounds, taps, w, bias=None, gelu=False, res=None, stats=None, wrong=None):
+    """tedspad_mgfn_gemm: y[m, n] = sum_{t, c} A[m, t, c] w[n, t cin + c] + bias[n], then GELU, then + res. x (M, cin), w (N, taps * cin); stats (M, 2)
+    fp32 as handed (taps == 1): A = (x - mean) rs. Bound: z = the sum: (K + 2) u sum |A||w| with K = taps * cin (any order; + 2: the bias add and slack),
+    plus, with stats, the two roundings of every A element, u ((|x| + |mean|) |rs| + |A|), through |w|. GELU: its slope is at most 1.13, so 1.14 dz,
+    plus its own evaluation (mgfn_gelu_ref). Residual: one rounding of the sum, u (|y| + |res|)."""
+    A = mgfn_window(x, bounds, taps, wrong)
+    M, K = A.shape[0], taps * A.shape[2]
+    Aerr = torch.zeros_like(A)
+    if stats is not None:
+        mu, rs = stats[:, 0].to(D).view(M, 1, 1), stats[:, 1].to(D).view(M, 1, 1)
+        A0 = A
+        A = (A0 - mu) * rs
+        Aerr = U * ((A0.abs() + mu.abs()) * rs.abs() + A.abs())
+    w = w.to(D).reshape(-1, K)
+    z = A.reshape(M, K) @ w.t()
+    za = A.reshape(M, K).abs() @ w.abs().t()
+    if bias is not None:
+        z, za = z + bias.to(D), za + bias.to(D).abs()
+    b = (K + 2) * U * za + Aerr.reshape(M, K) @ w.abs().t()
+    if gelu:
+        z, be = mgfn_gelu_ref(z)
+        b = 1.14 * b + be
+    if res is not None:
+        b = b + U * (z.abs() + res.to(D).abs())
+        z = z + res.to(D)
+    return z, b + FLOOR32
+
+
+def mgfn_ln_stats_ref(x, eps, torch_ln):
+    """tedspad_mgfn_ln_stats: mean, rs = 1 / (std + eps) (MGFN) or 1 / sqrt(var + eps) (nn.LayerNorm), biased variance. Returns mean, rs, dmean, drs.
+    n = chain_row(C). dmean = (n + 2) u sum |x| / C. The second pass sums (x - mean~)^2 around the COMPUTED mean: sum (x - mean~)^2 / C = var + (mean -
+    mean~)^2 exactly, so dvar = dmean^2 + (n + 4) u (var + dmean^2) (each term: 2 roundings of the difference squared, one of the product). A one-pass
+    E[x^2] - mean^2 does not meet this. sqrt: |sqrt a~ - sqrt a| <= min(|a~ - a| / sqrt a, sqrt |a~ - a|), + K_SQRT u; the adds one rounding each; the
+    reciprocal: d(1 / den) <= dden / (den (den - dden)) + u / den."""
+    x = x.to(D)
+    C, n, eps = x.shape[1], chain_row(x.shape[1]), f32(eps)
+    mu = x.mean(1)
+    dmu = (n + 2) * U * x.abs().sum(1) / C
+    var = ((x - mu[:, None]) ** 2).mean(1)
+    dvar = dmu ** 2 + (n + 4) * U * (var + dmu ** 2)
+    if torch_ln:
+        den = (var + eps).sqrt()
+        dden = (dvar + U * (var + eps)) / den + K_SQRT * U * den
+    else:
+        std = var.sqrt()
+        den = std + eps
+        dden = torch.minimum(dvar / std.clamp_min(1e-300), dvar.sqrt()) + K_SQRT * U * std + U * den
+    rs = 1.0 / den
+    drs = torch.where(dden < den, dden / (den * (den - dden).clamp_min(1e-300)), torch.full_like(den, float("inf"))) + U * rs
+    return mu, rs, dmu, drs
+
+
+def mgfn_ln_apply_ref(x, stats, g, b):
+    """tedspad_mgfn_ln_apply with the fp32 stats it is handed: y = (x - mean) rs g + b. Bound: the difference one rounding, u (|x| + |mean|) |rs g|; two
+    products and the add: 3 u |(x - mean) rs g| + u |y|."""
+    x, g, b = x.to(D), g.to(D), b.to(D)
+    mu, rs = stats[:, 0:1].to(D), stats[:, 1:2].to(D)
+    t = (x - mu) * rs * g
+    return t + b, U * (x.abs() + mu.abs()) * (rs * g).abs() + 3 * U * t.abs() + U * (t + b).abs() + FLOOR32
+
+
+def mgfn_ln_bwd_ref(dy, x, stats, g, torch_ln, eps, add=None):
+    """tedspad_mgfn_ln_bwd with the fp32 stats it is handed. d = dy g, xh = (x - mean) rs, s1 = mean_c d, s2 = mean_c d xh, k = rs (nn.LayerNorm) or
+    1 / (1 / rs - eps) (MGFN: 1 / std), dx = (d - s1) rs - xh s2 k (+ add). Bound, n = chain_row(C): exh = u ((|x| + |mean|) |rs| + |xh|); ds1 = (n + 2) u
+    mean |d|; ds2 = (n + 3) u mean |d xh| + mean |d| exh; MGFN: 1 / rs and the subtraction round once each, dsd = u (|1 / rs| + |sd|), dk = |k| (dsd / |sd|)
+    / (1 - dsd / |sd|) + u |k|; then every product and difference one rounding. A constant row has sd = 0 in the MGFN flavour: the reference divides by
+    zero there as the formula does (inf / nan)."""
+    dy, x, g = dy.to(D), x.to(D), g.to(D)
+    C, n, eps = x.shape[1], chain_row(x.shape[1]), f32(eps)
+    mu, rs = stats[:, 0:1].to(D), stats[:, 1:2].to(D)
+    xh = (x - mu) * rs
+    exh = U * ((x.abs() + mu.abs()) * rs.abs() + xh.abs())
+    d = dy * g
+    s1 = d.mean(1, keepdim=True)
+    ds1 = (n + 2) * U * d.abs().mean(1, keepdim=True)
+    s2 = (d * xh).mean(1, keepdim=True)
+    ds2 = (n + 3) * U * (d * xh).abs().mean(1, keepdim=True) + (d.abs() * exh).mean(1, keepdim=True)
+    if torch_ln:
+        k, dk = rs, torch.zeros_like(rs)
+    else:
+        inv = 1.0 / rs
+        sd = inv - eps
+        k = 1.0 / sd
+        r = U * (inv.abs() + sd.abs()) / sd.abs()
+        dk = k.abs() * r / (1.0 - r) + U * k.abs()
+    k2 = s2 * k
+    dk2 = ds2 * k.abs() + s2.abs() * dk + U * k2.abs()
+    t1 = (d - s1) * rs
+    e1 = rs.abs() * (U * d.abs() + ds1 + U * (d - s1).abs()) + U * t1.abs()
+    t2 = xh * k2
+    e2 = exh * k2.abs() + xh.abs() * dk2 + U * t2.abs()
+    dx = t1 - t2
+    b = e1 + e2 + U * (t1.abs() + t2.abs())
+    if add is not None:
+        dx = dx + add.to(D)
+        b = b + U * (dx.abs() + add.to(D).abs())
+    return dx, b + FLOOR32
+
+
+def _inv_sqrt(var, dvar, eps):
+    """1 / sqrt(var + eps) and its bound (see mgfn_ln_stats_ref)."""
+    den = (var + eps).sqrt()
+    dden = (dvar + U * (var + eps)) / den + K_SQRT * U * den
+    inv = 1.0 / den
+    return inv, torch.where(dden < den, dden / (den * (den - dden).clamp_min(1e-300)), torch.full_like(den, float("inf"))) + U * inv
+
+
+def mgfn_bn_fwd_ref(x, gamma, beta, eps, momentum, running_mean=None, running_var=None, wrong=None):
+    """tedspad_mgfn_bn_train_fwd: nn.BatchNorm1d over all M tokens in train mode. M = 1: the kernel's documented rule, running_var takes the biased
+    variance (0). Returns a dict of (value, bound): y, mean, invstd, running_mean, running_var. n = chain_tokens(M): dmean = (n + 2) u sum |x| / M;
+    dvar = dmean^2 + (n + 5) u (var + dmean^2) (the second pass is centred on the computed mean: see mgfn_ln_stats_ref); invstd: _inv_sqrt; y = xh gamma +
+    beta with dxh = (dmean + u (|x| + |mean|)) invstd + |x - mean| dinvstd + u |xh|, then |gamma| dxh + 2 u |xh gamma| + u |y|; the running statistics:
+    momentum times the error of the statistic (the variance times M / (M - 1)), plus 3 u on each term. wrong = 'biased_running_var'."""
+    x, gamma, beta = x.to(D), gamma.to(D), beta.to(D)
+    M, n, eps, mom = x.shape[0], chain_tokens(x.shape[0]), f32(eps), f32(momentum)
+    mean = x.mean(0)
+    dmu = (n + 2) * U * x.abs().sum(0) / M
+    d = x - mean
+    var = (d * d).mean(0)
+    dvar = dmu ** 2 + (n + 5) * U * (var + dmu ** 2)
+    inv, dinv = _inv_sqrt(var, dvar, eps)
+    xh = d * inv
+    dxh = (dmu + U * (x.abs() + mean.abs())) * inv + d.abs() * dinv + U * xh.abs()
+    t = xh * gamma
+    out = {"y": (t + beta, gamma.abs() * dxh + 2 * U * t.abs() + U * (t + beta).abs() + FLOOR32), "mean": (mean, dmu + U * mean.abs() + FLOOR32),
+           "invstd": (inv, dinv + FLOOR32), "running_mean": None, "running_var": None}
+    if running_mean is not None:
+        rm, rv = running_mean.to(D), running_var.to(D)
+        f = M / (M - 1.0) if (M > 1 and wrong != "biased_running_var") else 1.0
+        out["running_mean"] = ((1 - mom) * rm + mom * mean, mom * dmu + 3 * U * ((1 - mom) * rm.abs() + mom * mean.abs()) + FLOOR32)
+        out["running_var"] = ((1 - mom) * rv + mom * var * f, mom * f * (dvar + 2 * U * var) + 3 * U * ((1 - mom) * rv.abs() + mom * var * f) + FLOOR32)
+    return out
+
+
+def mgfn_bn_bwd_ref(dy, x, stat, gamma, add=None):
+    """tedspad_mgfn_bn_train_bwd with the fp32 stat (mean | invstd, 2 C) it is handed: dbeta = sum dy, dgamma = sum dy xh, dx = gamma invstd (dy - dbeta / M
+    - xh dgamma / M) (+ add). Returns a dict of (value, bound). n = chain_tokens(M): ddbeta = (n + 1) u sum |dy|; exh = u ((|x| + |mean|) invstd + |xh|);
+    ddgamma = (n + 2) u sum |dy xh| + sum |dy| exh; dx from the COMPUTED sums: their errors / M, exh |dgamma| / M, and 3 u on each of the three terms (1 / M,
+    the products, the differences); the outer products 2 u, the add one."""
+    dy, x, gamma = dy.to(D), x.to(D), gamma.to(D)
+    M, C = x.shape
+    n = chain_tokens(M)
+    mean, inv = stat[:C].to(D), stat[C:].to(D)
+    xh = (x - mean) * inv
+    exh = U * ((x.abs() + mean.abs()) * inv.abs() + xh.abs())
+    dbeta, ddb = dy.sum(0), (n + 1) * U * dy.abs().sum(0)
+    dgamma, ddg = (dy * xh).sum(0), (n + 2) * U * (dy * xh).abs().sum(0) + (dy.abs() * exh).sum(0)
+    inner = dy - dbeta / M - xh * dgamma / M
+    einner = ddb / M + exh * dgamma.abs() / M + xh.abs() * ddg / M + 3 * U * (dy.abs() + dbeta.abs() / M + (xh * dgamma).abs() / M)
+    gi = gamma * inv
+    dx = gi * inner
+    b = gi.abs() * einner + 2 * U * dx.abs()
+    if add is not None:
+        dx = dx + add.to(D)
+        b = b + U * (dx.abs() + add.to(D).abs())
+    return {"dx": (dx, b + FLOOR32), "dgamma": (dgamma, ddg + FLOOR32), "dbeta": (dbeta, ddb + FLOOR32)}
+
+
+def mgfn_head_ref(x, ln_w, ln_b, fc_w, fc_b, eps):
+    """tedspad_mgfn_head: h = nn.LayerNorm(C)(x), logit = h . fc_w + fc_b, score = sigmoid(logit), mag = ||h||_2. Returns a dict of (value, bound).
+    Statistics and their errors: mgfn_ln_stats_ref (torch flavour). dxh = (dmean + u (|x| + |mean|)) rs + |x - mean| drs + u |xh|; dh = |ln_w| dxh + u |xh
+    ln_w| + u |h|; dlogit = sum dh |fc_w| + (n + 3) u (sum |h fc_w| + |fc_b|); score = 1 / (1 + exp(-z)): a relative error r of the exponential moves it by
+    s (1 - s) r, so s (1 - s) (dlogit + K_EXP u) (1 + 2 (dlogit + K_EXP u)) + 3 u s; mag: dn2 = sum (2 |h| dh + dh^2) + (n + 3) u sum h^2, then min(dn2 /
+    mag, sqrt dn2) + K_SQRT u mag."""
+    x, lw, lb, fw = x.to(D), ln_w.to(D), ln_b.to(D), fc_w.to(D)
+    n, fb = chain_row(x.shape[1]), f32(fc_b)
+    mu, rs, dmu, drs = mgfn_ln_stats_ref(x, eps, 1)
+    mu, rs, dmu, drs = (t[:, None] for t in (mu, rs, dmu, drs))
+    d = x - mu
+    xh = d * rs
+    dxh = (dmu + U * (x.abs() + mu.abs())) * rs + d.abs() * drs + U * xh.abs()
+    t = xh * lw
+    h = t + lb
+    dh = lw.abs() * dxh + U * t.abs() + U * h.abs() + FLOOR32
+    z = (h * fw).sum(1) + fb
+    dz = (dh * fw.abs()).sum(1) + (n + 3) * U * ((h * fw).abs().sum(1) + abs(fb)) + FLOOR32
+    s = torch.sigmoid(z)
+    r = dz + K_EXP * U
+    ds = s * (1 - s) * r * (1 + 2 * r) + 3 * U * s + FLOOR32
+    n2 = (h * h).sum(1)
+    dn2 = (2 * h.abs() * dh + dh * dh).sum(1) + (n + 3) * U * n2
+    mag = n2.sqrt()
+    dmag = torch.minimum(dn2 / mag.clamp_min(1e-300), dn2.sqrt()) + K_SQRT * U * mag + FLOOR32
+    return {"h": (h, dh), "logit": (z, dz), "score": (s, ds), "mag": (mag, dmag)}
+
+
+def mgfn_head_bwd_ref(score, dscore, fc_w, dh):
+    """tedspad_mgfn_head_bwd with the fp32 score it is handed: dz = dscore s (1 - s), dh += fc_w dz. Returns (dh, bound), (dz, bound). 1 - s rounds once
+    (absolute u |1 - s| <= u): u |dscore s| + 3 u |dz|; dh: |fc_w| ddz + u |fc_w dz| + u |dh|."""
+    s, ds, fw, dh = score.to(D), dscore.to(D), fc_w.to(D), dh.to(D)
+    z = ds * s * (1 - s)
+    dz = U * (ds * s).abs() + 3 * U * z.abs() + FLOOR32
+    out = dh + fw * z[:, None]
+    return (out, fw.abs() * dz[:, None] + U * (fw * z[:, None]).abs() + U * out.abs() + FLOOR32), (z, dz)
+
+
+def mgfn_crop_mean_ref(a, seg_off, ncrops):
+    """tedspad_mgfn_crop_mean: out[seg_off[v] + t] = mean_c a[ncrops seg_off[v] + c T_v + t]. Bound: (ncrops + 1) u mean |a|."""
+    a = a.to(D)
+    outs, bs = [], []
+    for v in range(len(seg_off) - 1):
+        s0, T = seg_off[v], seg_off[v + 1] - seg_off[v]
+        blk = a[ncrops * s0:ncrops * s0 + ncrops * T].view(ncrops, T)
+        outs.append(blk.mean(0))
+        bs.append((ncrops + 1) * U * blk.abs().mean(0) + FLOOR32)
+    return torch.cat(outs), torch.cat(bs)
+
+
+def mgfn_col_reduce_ref(a, mode, scale=1.0, x=None, st=None, wrong=None):
+    """tedspad_mgfn_col_reduce, with the fp32 st it is handed. (out0, bound0), (out1, bound1), each (C):
+    0: scale sum a | 0;  1: scale sum a | scale sum a (x - st[m, 0]) st[m, 1];  2: the same with the per-column st[c], st[C + c];  3: scale sum (a -
+    st[c])^2 | 0 (st None: mode 0);  4: scale sum st[m] a | scale sum st[m]. Bound, n = chain_tokens(M): (n + 2) u |scale| sum |terms| (any order inside the
+    chunk and over the chunks; + 2: the scale), plus per term the roundings that make it: xh = (x - mean) rs: u ((|x| + |mean|) |rs| + |xh|) times |a|, and
+    u |a xh|; (a - st)^2: 3 u; st[m] a: u. wrong = 'skip_last_chunk': a last partial chunk of MT_CHUNK tokens is left out."""
+    a = a.to(D)
+    M, C = a.shape
+    n, scale = chain_tokens(M), f32(scale)
+    if mode == 3 and st is None:
+        mode = 0
+    zero = torch.zeros_like(a)
+    if mode == 0:
+        t0, e0, t1, e1 = a, zero, zero, zero
+    elif mode in (1, 2):
+        st = st.to(D)
+        mu, rs = (st[:, 0:1], st[:, 1:2]) if mode == 1 else (st[:C], st[C:])
+        xh = (x.to(D) - mu) * rs
+        t0, e0, t1 = a, zero, a * xh
+        e1 = a.abs() * U * ((x.to(D).abs() + mu.abs()) * rs.abs() + xh.abs()) + U * t1.abs()
+    elif mode == 3:
+        d = a - st.to(D)[:C]
+        t0, e0, t1, e1 = d * d, 3 * U * d * d, zero, zero
+    else:
+        r = st.to(D)[:M, None]
+        t0, e0, t1, e1 = r * a, U * (r * a).abs(), r.expand(M, C), zero
+    rows = M - M % MT_CHUNK if (wrong == "skip_last_chunk" and M % MT_CHUNK) else M
+    out = []
+    for t, e in ((t0, e0), (t1, e1)):
+        out.append((scale * t[:rows].sum(0), abs(scale) * ((n + 2) * U * t.abs().sum(0) + e.sum(0)) + FLOOR32))
+    return out
+
+
+def mgfn_transpose_ref(x, bounds, taps, ldo):
+    """tedspad_mgfn_transpose: out[(t C + c), m] = x[m + t - taps // 2, c] inside m's sequence, 0 outside and for M <= m < ldo. A copy: exact."""
+    A = mgfn_window(x, bounds, taps)
+    M, _, C = A.shape
+    out = torch.zeros((taps * C, ldo), dtype=D)
+    out[:, :M] = A.permute(1, 2, 0).reshape(taps * C, M)
+    return out
+
+
+def mgfn_wgrad_slices(ldk, rows, N):
+    """(kslice, nslices) of tedspad_mgfn_wgrad, the launcher's own formula: enough slices for ~2048 waves, at least 128 tokens each."""
+    tiles = ((rows + 63) // 64) * (N // 64)
+    want = max(1, min((2048 + tiles - 1) // tiles, (ldk + 127) // 128))
+    ks = ((ldk + want - 1) // want + 15) // 16 * 16
+    return ks, (ldk + ks - 1) // ks
+
+
+def mgfn_wgrad_ref(at, dyt):
+    """tedspad_mgfn_wgrad: dwt (rows, N) = at (rows, ldk) . dyt (N, ldk)^T over the token axis. Bound: (ldk + slices + 2) u sum |at||dyt| (any order)."""
+    at, dyt = at.to(D), dyt.to(D)
+    ldk = at.shape[1]
+    ns = mgfn_wgrad_slices(ldk, at.shape[0], dyt.shape[0])[1]
+    return at @ dyt.t(), (ldk + ns + 2) * U * (at.abs() @ dyt.abs().t()) + FLOOR32
+
+
+def _head_of(C, heads, wrong=None):
+    c = torch.arange(C)
+    return c // (C // heads) if wrong == "head_block" else c % heads
+
+
+def mgfn_relpos_ref(v, bounds, heads, w, b, wrong=None):
+    """tedspad_mgfn_relpos: out[m, c] = b[c % heads] + sum_t w[c % heads, t] v[m + t - 2, c], zero outside the sequence. Bound: 7 u (|b| + sum |w||v|).
+    wrong = 'head_block': the filter of head c / (C / heads); 'leak': taps cross the sequence ends."""
+    A = mgfn_window(v, bounds, 5, "leak" if wrong == "leak" else None)
+    hd = _head_of(A.shape[2], heads, wrong)
+    wc, bc = w.to(D)[hd].t(), b.to(D)[hd]                                   # (5, C), (C)
+    return (A * wc).sum(1) + bc, 7 * U * ((A * wc).abs().sum(1) + bc.abs()) + FLOOR32
+
+
+def mgfn_relpos_bwd_ref(dout, v, bounds, heads, w):
+    """tedspad_mgfn_relpos_bwd: dv[m, c] = sum_t w[c % heads, t] dout[m - t + 2, c]; dw[h, j] = sum over m and the channels of head h of dout[m, c]
+    v[m + j - 2, c]; db[h] = the same sum of dout. Returns (dv, bound), (dw, bound), (db, bound). dv: 7 u sum |w||dout|. dw, db: the chain is MT_CHUNK
+    tokens in a chunk, then ceil(chunks * C / heads / 256) entries per thread and an 8-step tree: (that + 2) u sum |terms|."""
+    dout = dout.to(D)
+    M, C = dout.shape
+    hd = _head_of(C, heads)
+    wc = w.to(D)[hd].t()
+    B = mgfn_window(dout, bounds, 5).flip(1)                            # B[m, t] = dout[m - t + 2]
+    dv = (B * wc).sum(1)
+    A = mgfn_window(v, bounds, 5)
+    terms = dout[:, None, :] * A                                        # (M, 5, C)
+    nch, per = (M + MT_CHUNK - 1) // MT_CHUNK, C // heads
+    n = MT_CHUNK + (nch * per + 255) // 256 + 8 + 2
+    sel = torch.zeros((C, heads), dtype=D)
+    sel[torch.arange(C), hd] = 1.0
+    dw, dwa = (terms.sum(0) @ sel).t(), (terms.abs().sum(0) @ sel).t()   # (heads, 5)
+    db, dba = dout.sum(0) @ sel, dout.abs().sum(0) @ sel
+    return (dv, 7 * U * (B * wc).abs().sum(1) + FLOOR32), (dw, n * U * dwa + FLOOR32), (db, n * U * dba + FLOOR32)
+
+
+def _att_rows(q, k, wrong=None):
+    """Per (sequence, head): logits S = (q / 8) k^T with their bound dS = 66 u sum |q / 8||k| (64 products, any order, + 2), the row maximum, the logit range R
+    (+ 2 max dS: the computed logits), the key blocks nb, and row = u (R + K_EXP + nb (K_EXP + R + 3)): the relative error of one unnormalised weight exp(s - m)
+    beyond dS: the subtraction (u |s - m| <= u R), expf, and per key block one rescale by exp(m_old - m_new) (argument u R, expf, two products)."""
+    T = q.shape[0]
+    qs = q * (1.0 if wrong == "no_scale" else 0.125)
+    S = qs @ k.t()
+    dS = 66 * U * (qs.abs() @ k.abs().t())
+    nb = (T + 31) // 32
+    R = S.max(1).values - S.min(1).values + 2 * dS.max(1).values
+    return qs, S, dS, nb, R, U * (R + K_EXP + nb * (K_EXP + R + 3))
+
+
+def mgfn_attention_ref(qkv, off, heads, wrong=None):
+    """tedspad_mgfn_attention: out[m, h 64 + d] = sum_j softmax_j((q_m / 8) . k_j) v_j[d] over m's sequence; qkv rows = q | k | v, each heads x 64. Bound: with
+    eps_ij = expm1(dS_ij) + row_i the relative error of weight j of row i (_att_rows), the numerator sum_j e_j v_jd (T terms on the MFMA) is off by
+    sum_j e_j |v_jd| (eps_ij + (T + 2) u), the denominator by sum_j e_j eps_ij + (T + nb + 3) u sum_j e_j; so |out~ - out| <= sum_j p_j |v_jd| (eps_ij + (T + 2) u)
+    + (sum_j p_j |v_jd|) (sum_j p_j eps_ij + (T + nb + 3) u), times 1 + 4 max eps for the second order. wrong = 'no_scale': softmax of q . k; 'drop_block':
+    the last (partial) key block of a sequence longer than 32 is left out."""
+    qkv = qkv.to(D)
+    M, inner = qkv.shape[0], 64 * heads
+    out, bnd = torch.zeros((M, inner), dtype=D), torch.zeros((M, inner), dtype=D)
+    for s in range(len(off) - 1):
+        b0, b1 = off[s], off[s + 1]
+        T = b1 - b0
+        for h in range(heads):
+            q, k, v = (qkv[b0:b1, j * inner + h * 64:j * inner + (h + 1) * 64] for j in range(3))
+            if wrong == "drop_block" and T > 32:
+                keep = (T - 1) // 32 * 32
+                k, v = k[:keep], v[:keep]
+            _, S, dS, nb, R, row = _att_rows(q, k, wrong)
+            p = torch.softmax(S, 1)
+            eps = torch.expm1(dS) + row[:, None]
+            pv = p @ v.abs()
+            b = (p * (eps + (T + 2) * U)) @ v.abs() + pv * ((p * eps).sum(1) + (T + nb + 3) * U)[:, None]
+            out[b0:b1, h * 64:(h + 1) * 64] = p @ v
+            bnd[b0:b1, h * 64:(h + 1) * 64] = b * (1 + 4 * float(eps.max())) + FLOOR32
+    return out, bnd
+
+
+def mgfn_attention_bwd_ref(qkv, o, dO, off, heads):
+    """tedspad_mgfn_attention_bwd with the fp32 forward output o it is handed. P = softmax(S), D_i = dO_i . o_i, dP = dO V^T, dS = P (dP - D), dq = dS K / 8,
+    dk = dS^T q / 8, dv = P^T dO; lse (M, heads, 2) = the row's log-sum-exp L and D. Returns (dqkv (M, 3 inner), bound), (lse, bound).
+    dL = max_j dS_ij + row_i + (T + 2) u (the sum of the weights) + K_LOG u |log l| + u |L|; the recomputed p~ = exp(s~ - L~): epsP = expm1(dS) + dL +
+    u |s - L| + K_EXP u relative; dD = 66 u sum |dO||o|, ddP = 66 u sum |dO||v|; ddS = p (epsP |dP - D| + ddP + dD + u (|dP| + |D|)) + 2 u |dS|; then each
+    product over T terms: dq: (sum_j ddS |k| + (T + 3) u sum_j |dS||k|) / 8, dk alike over the queries, dv: sum_i p |dO| (epsP + (T + 3) u); all times
+    1 + 4 max epsP."""
+    qkv, o, dO = qkv.to(D), o.to(D), dO.to(D)
+    M, inner = qkv.shape[0], 64 * heads
+    dqkv, bnd = torch.zeros((M, 3 * inner), dtype=D), torch.zeros((M, 3 * inner), dtype=D)
+    lse, blse = torch.zeros((M, heads, 2), dtype=D), torch.zeros((M, heads, 2), dtype=D)
+    for s in range(len(off) - 1):
+        b0, b1 = off[s], off[s + 1]
+        T = b1 - b0
+        for h in range(heads):
+            cs = [slice(j * inner + h * 64, j * inner + (h + 1) * 64) for j in range(3)]
+            q, k, v = (qkv[b0:b1, c] for c in cs)
+            oh, dh = o[b0:b1, cs[0]], dO[b0:b1, cs[0]]
+            qs, S, dS, nb, R, row = _att_rows(q, k)
+            L = torch.logsumexp(S, 1)
+            logl = L - S.max(1).values
+            dL = dS.max(1).values + row + (T + 2) * U + K_LOG * U * logl.abs() + U * L.abs()
+            p = torch.exp(S - L[:, None])
+            epsP = torch.expm1(dS) + dL[:, None] + U * (S - L[:, None]).abs() + K_EXP * U
+            Dr, dD = (dh * oh).sum(1), 66 * U * (dh * oh).abs().sum(1)
+            dP, ddP = dh @ v.t(), 66 * U * (dh.abs() @ v.abs().t())
+            G = dP - Dr[:, None]
+            dSg = p * G
+            ddS = p * (epsP * G.abs() + ddP + dD[:, None] + U * (dP.abs() + Dr.abs()[:, None])) + 2 * U * dSg.abs()
+            so = 1 + 4 * float(epsP.max())
+            dqkv[b0:b1, cs[0]] = dSg @ k * 0.125
+            bnd[b0:b1, cs[0]] = 0.125 * (ddS @ k.abs() + (T + 3) * U * (dSg.abs() @ k.abs())) * so + FLOOR32
+            dqkv[b0:b1, cs[1]] = dSg.t() @ qs
+            bnd[b0:b1, cs[1]] = (ddS.t() @ qs.abs() + (T + 3) * U * (dSg.abs().t() @ qs.abs())) * so + FLOOR32
+            dqkv[b0:b1, cs[2]] = p.t() @ dh
+            bnd[b0:b1, cs[2]] = ((p * (epsP + (T + 3) * U)).t() @ dh.abs()) * so + FLOOR32
+            lse[b0:b1, h, 0], blse[b0:b1, h, 0] = L, dL + FLOOR32
+            lse[b0:b1, h, 1], blse[b0:b1, h, 1] = Dr, dD + FLOOR32
+    return (dqkv, bnd), (lse, blse)
+
+
+def worst(got, ref, bound):
+    """'' if every element of got is within its bound of ref (and finite), else the number of offenders and the worst one's index, error and bound."""
+    got, ref, bound = torch.as_tensor(got).to(D), torch.as_tensor(ref).to(D), torch.as_tensor(bound).to(D)
+    assert got.shape == ref.shape == bound.shape, (got.shape, ref.shape, bound.shape)
+    err = (got - ref).abs()
+    bad = ~(err <= bound)                                               # a NaN on either side is an offender
+    if not bool(bad.any()):
+        return ""
+    ratio = torch.where(bad, torch.nan_to_num(err / bound, nan=float("inf")), torch.zeros_like(err))
+    idx = tuple(int(i) for i in (ratio == ratio.max()).nonzero()[0])
+    return "%d of %d out of bound; worst at %s: got %r, want %r, error %.3e, bound %.3e" % (
+        int(bad.sum()), bad.numel(), idx, float(got[idx]), float(ref[idx]), float(err[idx]), float(bound[idx]))
+
+
+# shapes of tests/test_hip_mgfn_edges.py
+MGFN_GEMM_M = (1, 63, 64, 65, 255, 256, 257)
+MGFN_GEMM_N = (64, 128)
+MGFN_GEMM_TAPS_CIN = ((1, 16), (1, 48), (3, 16), (3, 48), (5, 32))
+MGFN_ATT_LENGTHS = (1, 31, 32, 33, 64, 65)
+MGFN_ROW_C = (4, 252, 256, 260)
+MGFN_ROW_M = (1, 3, 4, 5)
+MGFN_COL_C = (1, 63, 64, 65, 255, 256, 257)
+MGFN_COL_M = (1, 127, 128, 129, 385)
+MGFN_WGRAD_M = (1, 15, 16, 17, 128, 129, 300)
+
+
+def gemm_lengths(M):
+    """Sequence lengths summing to M with ends exactly on rows 32, 64 and 256 and one row either side of them (where M reaches), and a run of length-1
+    sequences (only the centre tap survives)."""
+    ends = sorted({e for e in (1, 2, 3, 4, 31, 32, 33, 63, 64, 65, 255, 256, 257) if e < M} | {M})
+    return [b - a for a, b in zip([0] + ends[:-1], ends)]

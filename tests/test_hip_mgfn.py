@@ -11,6 +11,7 @@ import torch
 import torch.nn.functional as F
 
 from conftest import GOLDEN_DIR, rel_l2
+from kernel_refs import mgfn_attention_torch, mgfn_conv_seq as _conv_seq, mgfn_relpos_torch, mgfn_seqs as _seqs
 from ted_spad_amd import _lib
 from ted_spad_amd.engine import _stream_ptr
 from ted_spad_amd.synth import synth_mgfn_state_dict, synth_tensor
@@ -39,19 +40,10 @@ def _ragged(lengths):
     return off.tolist(), bounds, off.to(torch.int32).cuda()
 
 
-def _seqs(x, off):
-    return [x[off[i]:off[i + 1]] for i in range(len(off) - 1)]
-
-
 def _check(name, got, ref):
     e = rel_l2(got.detach().cpu().double().numpy(), ref.detach().cpu().numpy())
     print("%-28s rel-L2 %.2e" % (name, e))
     assert e <= BOUND, (name, e)
-
-
-def _conv_seq(x, w, b, taps):
-    # x (T, cin) one sequence, w (N, taps, cin) -> Conv1d(padding=taps//2) over time, fp64
-    return F.conv1d(x.t().unsqueeze(0), w.permute(0, 2, 1), b, padding=taps // 2)[0].t()
 
 
 @pytest.mark.parametrize("mode", ["to_tokens_k3x2049", "scc_k3", "ln_gelu_res", "plain_res"])
@@ -99,13 +91,7 @@ def test_attention_vs_fp64(heads):
     qc = qkv.cuda()
     _lib.check(_lib.lib().tedspad_mgfn_attention(qc.data_ptr(), 3 * inner, off_d.data_ptr(), len(lengths), max(lengths), heads, out.data_ptr(),
                                                  inner, _stream_ptr()))
-    refs = []
-    for s in _seqs(qkv.double(), off):
-        T = s.shape[0]
-        q, k, v = (t.reshape(T, heads, 64).transpose(0, 1) for t in s.chunk(3, dim=1))
-        a = torch.softmax((q * 0.125) @ k.transpose(1, 2), -1) @ v
-        refs.append(a.transpose(0, 1).reshape(T, inner))
-    _check("attention heads=%d" % heads, out, torch.cat(refs))
+    _check("attention heads=%d" % heads, out, mgfn_attention_torch(qkv, off, heads, torch.float64))
 
 
 @pytest.mark.parametrize("heads", [1, 16])
@@ -119,9 +105,7 @@ def test_relpos_vs_fp64(heads):
     vc, wc, bc = v.cuda(), w.cuda(), b.cuda()
     _lib.check(_lib.lib().tedspad_mgfn_relpos(vc.data_ptr(), C, bounds.data_ptr(), M, C, heads, wc.data_ptr(), bc.data_ptr(), out.data_ptr(), C,
                                               _stream_ptr()))
-    # utils.py:144-146: 'b (c h) t -> (b c) h t' gives channel ch the filter of head ch % heads
-    wf, bf = w.double().repeat(C // heads, 1).unsqueeze(1), b.double().repeat(C // heads)
-    ref = torch.cat([F.conv1d(s.t().unsqueeze(0), wf, bf, padding=2, groups=C)[0].t() for s in _seqs(v.double(), off)])
+    ref = mgfn_relpos_torch(v, w, b, off, heads, torch.float64)
     _check("relpos heads=%d" % heads, out, ref)
 
 

@@ -7,6 +7,7 @@ import torch
 import torch.nn.functional as F
 
 from conftest import rel_l2
+from kernel_refs import mgfn_attention_torch, mgfn_conv_autograd as _conv_ref, mgfn_relpos_torch
 from ted_spad_amd import _lib
 from ted_spad_amd import mgfn as K
 from ted_spad_amd.engine import _stream_ptr
@@ -29,10 +30,6 @@ def _ragged(lengths):
     return off.tolist(), bounds, off.to(torch.int32).cuda()
 
 
-def _seqs(x, off):
-    return [x[off[i]:off[i + 1]] for i in range(len(off) - 1)]
-
-
 def _check(name, got, ref, ref32=None):
     """rel-L2 of got against the fp64 ref within BOUND, or (ref32 given: torch's fp32 CPU result) within 10x ref32's own error."""
     ref = ref.detach().cpu().double().numpy()
@@ -45,19 +42,6 @@ def _check(name, got, ref, ref32=None):
     else:
         print("%-36s rel-L2 %.2e" % (name, e))
     assert e <= bound, (name, e, bound)
-
-
-def _conv_seq(x, w, b, taps):
-    # x (T, cin) one sequence, w (N, taps, cin) -> Conv1d(padding = taps // 2) over time
-    return F.conv1d(x.t().unsqueeze(0), w.permute(0, 2, 1), b, padding=taps // 2)[0].t()
-
-
-def _conv_ref(x, w, b, taps, off, dy):
-    """(dx, dw, db) of sum(conv(x) * dy) by autograd in x's dtype."""
-    x, w, b = x.clone().requires_grad_(True), w.clone().requires_grad_(True), b.clone().requires_grad_(True)
-    y = torch.cat([_conv_seq(s, w, b, taps) for s in _seqs(x, off)])
-    (y * dy).sum().backward()
-    return x.grad, w.grad, b.grad
 
 
 WG = {"k3_80x64": (3, 80, 64), "k3_128x128": (3, 128, 128), "k1_1024x4096": (1, 1024, 4096), "k1_4096x1024": (1, 4096, 1024)}
@@ -206,16 +190,9 @@ def test_attention_bwd_vs_fp64(heads):
     _lib.check(L.tedspad_mgfn_attention_bwd(qc.data_ptr(), 3 * inner, o.data_ptr(), inner, dc.data_ptr(), inner, off_d.data_ptr(), len(LENGTHS),
                                             max(LENGTHS), heads, lse.data_ptr(), dqkv.data_ptr(), 3 * inner, st))
     assert torch.equal(first, dqkv)
-    qd = qkv.double().requires_grad_(True)
-    outs = []
-    for s in _seqs(qd, off):
-        T = s.shape[0]
-        q, k, v = (t.reshape(T, heads, 64).transpose(0, 1) for t in s.chunk(3, dim=1))
-        a = torch.softmax((q * 0.125) @ k.transpose(1, 2), -1) @ v
-        outs.append(a.transpose(0, 1).reshape(T, inner))
-    (torch.cat(outs) * do.double()).sum().backward()
+    _, grad = mgfn_attention_torch(qkv, off, heads, torch.float64, do)
     for name, sl in (("dq", slice(0, inner)), ("dk", slice(inner, 2 * inner)), ("dv", slice(2 * inner, 3 * inner))):
-        _check("attention bwd %s heads=%d" % (name, heads), dqkv[:, sl], qd.grad[:, sl])
+        _check("attention bwd %s heads=%d" % (name, heads), dqkv[:, sl], grad[:, sl])
 
 
 @pytest.mark.parametrize("heads", [2, 16])
@@ -235,13 +212,10 @@ def test_relpos_bwd_vs_fp64(heads):
                                              dv.data_ptr(), C, dw.data_ptr(), db.data_ptr(), st))
         outs.append((dv.clone(), dw.clone(), db.clone()))
     assert all(torch.equal(p, q) for p, q in zip(*outs))
-    vd, wd, bd = v.double().requires_grad_(True), w.double().requires_grad_(True), torch.zeros(heads, dtype=torch.float64, requires_grad=True)
-    wf, bf = wd.repeat(C // heads, 1).unsqueeze(1), bd.repeat(C // heads)                 # channel ch uses filter ch % heads
-    y = torch.cat([F.conv1d(s.t().unsqueeze(0), wf, bf, padding=2, groups=C)[0].t() for s in _seqs(vd, off)])
-    (y * do.double()).sum().backward()
-    _check("relpos bwd dv heads=%d" % heads, outs[0][0], vd.grad)
-    _check("relpos bwd dw heads=%d" % heads, outs[0][1], wd.grad)
-    _check("relpos bwd db heads=%d" % heads, outs[0][2], bd.grad)
+    _, dv64, dw64, db64 = mgfn_relpos_torch(v, w, torch.zeros(heads), off, heads, torch.float64, do)
+    _check("relpos bwd dv heads=%d" % heads, outs[0][0], dv64)
+    _check("relpos bwd dw heads=%d" % heads, outs[0][1], dw64)
+    _check("relpos bwd db heads=%d" % heads, outs[0][2], db64)
 
 
 def test_head_bwd_vs_fp64():

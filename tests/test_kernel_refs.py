@@ -1,5 +1,6 @@
 """CPU: the float64 references of tests/kernel_refs.py against float64 torch (autograd) at the shapes the -m gpu op tests use, to 1e-12 relative, and the
-properties of the two value generators those tests rely on (ties in the max-pool windows, exactness of dyadic sums)."""
+properties of the two value generators those tests rely on (ties in the max-pool windows, exactness of dyadic sums). Last, the MGFN references: equal to float64
+torch, torch's fp32 evaluation inside every per-element bound, a list of wrong references outside."""
 import numpy as np
 import pytest
 import torch
@@ -726,3 +727,359 @@ def test_fold_and_unpack_refs_equal_the_host_formulas():
     view = dw[:co, :9 * cink].view(co, 1, 3, 3, cink).permute(0, 4, 1, 2, 3)[:, :ci] * torch.from_numpy(rs).float().view(-1, 1, 1, 1, 1)
     g0 = np.arange(co * ci * 9, dtype=np.float64).reshape(co, ci, 1, 3, 3)
     assert np.array_equal(R.wgrad_unpack_ref(dw.numpy(), co, ci, k, cink, kpad, rs, g0), view.double().numpy() + g0)
+
+
+# ---- the MGFN references and their per-element bounds (tests/test_hip_mgfn_edges.py) -------------------------------------------------------------------------
+# (a) every reference equals float64 torch (autograd / F.conv1d / F.layer_norm / nn.BatchNorm1d / softmax attention); (b) torch's own fp32 evaluation of the same
+# operation stays inside every bound, and each deliberately wrong reference leaves it in at least one element. Where a kernel is handed fp32 statistics, the fp32
+# evaluation is handed the same ones.
+U = R.U
+F32T = torch.float32
+
+
+def inside(got, ref_bound, what):
+    ref, bound = ref_bound
+    msg = R.worst(got, ref, bound)
+    assert not msg, "%s: %s" % (what, msg)
+
+
+def outside(wrong_value, ref_bound, what):
+    ref, bound = ref_bound
+    assert R.worst(wrong_value, ref, bound), "%s: the wrong reference stays inside the bound" % what
+
+
+def not_vacuous(ref_bound, what, rel=1e-3):
+    """a bound far above fp32 rounding would accept anything: no element's bound exceeds rel * (the tensor's largest magnitude + 1)"""
+    ref, bound = ref_bound
+    assert float(bound.max()) <= rel * (float(ref.abs().max()) + 1.0), (what, float(bound.max()), float(ref.abs().max()))
+
+
+def test_mgfn_transcendental_constants():
+    """The worst per-element ratio |fp32 - float64| / (2^-24 |float64|) of torch's CPU expf, erff, logf, sqrtf on the same fp32 inputs (2 M points each);
+    measured 1.04 (exp on [-80, 80]), 1.05 (erf on [-6, 6] and on [-1e-3, 1e-3]), 1.03 (log on [1, 1e4]), 1.07 (sqrt). K_* = 11 >= 10x each."""
+    g = torch.Generator().manual_seed(0)
+    x = torch.rand(2000000, generator=g) * 2 - 1
+
+    def ratio(f, v):
+        a, b = f(v).double(), f(v.double())
+        return float(((a - b).abs() / (b.abs() * U))[b != 0].max())
+    got = {"exp": ratio(torch.exp, x * 80), "erf": max(ratio(torch.erf, x * 6), ratio(torch.erf, x * 1e-3)), "log": ratio(torch.log, 1 + x.abs() * 1e4),
+           "sqrt": ratio(torch.sqrt, x.abs() * 1e3 + 1e-6)}
+    print(got)
+    for name, K in (("exp", R.K_EXP), ("erf", R.K_ERF), ("log", R.K_LOG), ("sqrt", R.K_SQRT)):
+        assert 0.5 <= got[name] and 10 * got[name] <= K <= 15 * got[name], (name, got[name], K)
+
+
+_conv_tokens = R.mgfn_conv_tokens
+
+
+@pytest.mark.parametrize("taps,cin", R.MGFN_GEMM_TAPS_CIN)
+@pytest.mark.parametrize("M", [65, 257])
+def test_mgfn_gemm_ref(M, taps, cin):
+    N = 64
+    off, bounds = R.mgfn_ragged(R.gemm_lengths(M))
+    tag = "%d_%d_%d" % (M, taps, cin)
+    x = synth_tensor(41, "gx" + tag, (M, cin), -2, 2)
+    w3 = synth_tensor(41, "gw" + tag, (N, taps, cin), -1, 1) / (taps * cin) ** 0.5
+    bias, res = synth_tensor(41, "gb" + tag, (N,), -0.5, 0.5), synth_tensor(41, "gr" + tag, (M, N), -1, 1)
+    for gelu, with_res, with_bias in ((0, 0, 0), (1, 1, 1), (0, 1, 1), (1, 0, 0)):
+        def run(dt):
+            y = _conv_tokens(x.to(dt), off, w3.to(dt), bias.to(dt) if with_bias else None, taps)
+            y = F.gelu(y) if gelu else y
+            return y + res.to(dt) if with_res else y
+        rb = R.mgfn_gemm_ref(x, bounds, taps, w3.reshape(N, -1), bias if with_bias else None, gelu, res if with_res else None)
+        assert close(rb[0], run(D))
+        inside(run(F32T), rb, "gemm " + tag)
+        not_vacuous(rb, "gemm " + tag)
+        if taps > 1:
+            for wrong in ("leak", "reversed"):
+                outside(R.mgfn_gemm_ref(x, bounds, taps, w3.reshape(N, -1), bias if with_bias else None, gelu, res if with_res else None, wrong=wrong)[0], rb, wrong)
+    if taps == 1:                                                       # the LayerNorm prologue (MGFN flavour), statistics handed in fp32
+        mu, var = x.mean(1), x.var(1, unbiased=False)
+        st32 = torch.stack([mu, 1 / (var.sqrt() + 1e-5)], 1)
+        xd = x.to(D)
+        st64 = torch.stack([xd.mean(1), 1 / (xd.var(1, unbiased=False).sqrt() + 1e-5)], 1)
+        want = _conv_tokens((xd - st64[:, :1]) * st64[:, 1:], off, w3.to(D), bias.to(D), 1)
+        assert close(R.mgfn_gemm_ref(x, None, 1, w3.reshape(N, -1), bias, stats=st64)[0], want)
+        rb = R.mgfn_gemm_ref(x, None, 1, w3.reshape(N, -1), bias, True, res, stats=st32)
+        inside(F.gelu(_conv_tokens((x - st32[:, :1]) * st32[:, 1:], off, w3, bias, 1)) + res, rb, "gemm ln " + tag)
+        not_vacuous(rb, "gemm ln " + tag)
+
+
+_attention_torch = R.mgfn_attention_torch
+
+
+@pytest.mark.parametrize("heads", [1, 3])
+@pytest.mark.parametrize("scale", [2.0, 25.0], ids=["plain", "logits200"])
+def test_mgfn_attention_refs(heads, scale):
+    off, _ = R.mgfn_ragged(R.MGFN_ATT_LENGTHS)
+    M, inner = off[-1], 64 * heads
+    qkv = synth_tensor(42, "att%d" % heads, (M, 3 * inner), -1, 1)
+    qkv[:, :2 * inner] *= scale                                         # 25: |q . k| / 8 up to 64 * 625 / 8, logits of a few hundred
+    do = synth_tensor(42, "attdo%d" % heads, (M, inner), -1, 1)
+    o64, g64 = _attention_torch(qkv, off, heads, D, do)
+    o32, g32 = _attention_torch(qkv, off, heads, F32T, do)
+    fwd = R.mgfn_attention_ref(qkv, off, heads)
+    assert close(fwd[0], o64)
+    inside(o32, fwd, "attention")
+    not_vacuous(fwd, "attention", 1e-2 if scale > 2 else 1e-3)
+    bwd, lse = R.mgfn_attention_bwd_ref(qkv, o64, do, off, heads)
+    assert close(bwd[0], g64, 1e-10) and bool(torch.isfinite(bwd[1]).all()) and bool(torch.isfinite(lse[1]).all())
+    inside(g32, bwd, "attention bwd")
+    not_vacuous(bwd, "attention bwd", 0.05 if scale > 2 else 1e-3)
+    if scale == 2.0:
+        off33, _ = R.mgfn_ragged([33])
+        q33 = qkv[:33]
+        rb = R.mgfn_attention_ref(q33, off33, heads)
+        outside(R.mgfn_attention_ref(q33, off33, heads, wrong="drop_block")[0], rb, "a key block dropped for T = 33")
+        outside(R.mgfn_attention_ref(qkv, off, heads, wrong="no_scale")[0], fwd, "a softmax without the 1/8 scale")
+
+
+@pytest.mark.parametrize("heads,C", [(1, 64), (3, 192), (16, 1024)])
+def test_mgfn_relpos_refs(heads, C):
+    lengths = [1, 2, 3, 4, 5, 6, 110, 7]
+    off, bounds = R.mgfn_ragged(lengths)
+    M = off[-1]
+    v, do = synth_tensor(43, "rpv%d" % heads, (M, C), -1, 1), synth_tensor(43, "rpd%d" % heads, (M, C), -1, 1)
+    w, b = synth_tensor(43, "rpw%d" % heads, (heads, 5), -1, 1), synth_tensor(43, "rpb%d" % heads, (heads,), -0.5, 0.5)
+
+    run = lambda dt: R.mgfn_relpos_torch(v, w, b, off, heads, dt, do)          # noqa: E731
+    y64, dv64, dw64, db64 = run(D)
+    y32, dv32, dw32, db32 = run(F32T)
+    fwd = R.mgfn_relpos_ref(v, bounds, heads, w, b)
+    rdv, rdw, rdb = R.mgfn_relpos_bwd_ref(do, v, bounds, heads, w)
+    assert close(fwd[0], y64) and close(rdv[0], dv64) and close(rdw[0], dw64, 1e-10) and close(rdb[0], db64, 1e-10)
+    for got, rb, what in ((y32, fwd, "relpos"), (dv32, rdv, "relpos dv"), (dw32, rdw, "relpos dw"), (db32, rdb, "relpos db")):
+        inside(got, rb, what)
+        not_vacuous(rb, what, 1e-2 if what[-2:] in ("dw", "db") else 1e-3)          # dw, db: thousands of terms of mixed sign behind a small sum
+    outside(R.mgfn_relpos_ref(v, bounds, heads, w, b, wrong="leak")[0], fwd, "a tap read across a sequence end")
+    if heads > 1:
+        outside(R.mgfn_relpos_ref(v, bounds, heads, w, b, wrong="head_block")[0], fwd, "the filter of head ch / (C / heads)")
+
+
+def _hard_rows(x):
+    """row 1 (where there is one): 1000 + noise of 1e-2; row 2: constant 3"""
+    if x.shape[0] > 2:
+        x[1] = 1000.0 + 0.01 * x[1]
+        x[2] = 3.0
+    return x
+
+
+@pytest.mark.parametrize("torch_ln", [0, 1])
+@pytest.mark.parametrize("C", R.MGFN_ROW_C)
+def test_mgfn_layernorm_refs(C, torch_ln):
+    M, eps = 5, 1e-5
+    x = _hard_rows(synth_tensor(44, "lnx%d" % C, (M, C), -3, 5))
+    g, b = synth_tensor(44, "lng%d" % C, (C,), 0.5, 1.5), synth_tensor(44, "lnb%d" % C, (C,), -0.5, 0.5)
+    dy, add = synth_tensor(44, "lnd%d" % C, (M, C), -1, 1), synth_tensor(44, "lna%d" % C, (M, C), -1, 1)
+    xd = x.to(D)
+    mu, rs, dmu, drs = R.mgfn_ln_stats_ref(x, eps, torch_ln)
+    e32 = R.f32(eps)
+    var = xd.var(1, unbiased=False)
+    assert close(mu, xd.mean(1)) and close(rs, 1 / (var + e32).sqrt() if torch_ln else 1 / (var.sqrt() + e32))
+    assert float(rs[2]) == (1 / e32 ** 0.5 if torch_ln else 1 / e32)                       # the constant row
+    mu32, var32 = x.mean(1), x.var(1, unbiased=False)
+    rs32 = 1 / (var32 + eps).sqrt() if torch_ln else 1 / (var32.sqrt() + eps)
+    inside(mu32, (mu, dmu), "ln mean")
+    inside(rs32, (rs, drs), "ln rs")
+    # plain rows: 1e-5 of rs; 1000 + 1e-2 noise: a few per cent; the constant row: nothing says that a sum of equal values is exact, so the MGFN flavour's
+    # bound there is dmean against eps (the GPU test asserts the exact value instead)
+    assert bool((drs[[0, 3, 4]] <= 1e-5 * rs[[0, 3, 4]]).all()) and float(drs[1]) <= 0.05 * float(rs[1]) and (not torch_ln or float(drs[2]) <= 1e-5 * float(rs[2]))
+    onepass = (xd * xd).mean(1).float().double() - mu32.double() ** 2                                      # E[x^2] - mean^2 with one fp32 rounding of E[x^2]
+    bad = 1 / (onepass.clamp_min(0) + e32).sqrt() if torch_ln else 1 / (onepass.clamp_min(0).sqrt() + e32)
+    assert abs(float(bad[1] - rs[1])) > float(drs[1]), "a one-pass variance meets the bound of the 1000 + noise row"
+    outside(1 / (var + e32).sqrt() if not torch_ln else 1 / (var.sqrt() + e32), (rs, drs), "sqrt(var + eps) in place of std + eps")
+    # apply and backward, statistics handed in fp32
+    keep = [0, 1, 3, 4] if not torch_ln else [0, 1, 2, 3, 4]                                               # MGFN flavour: the constant row divides by zero
+    st64, st32 = torch.stack([mu, rs], 1), torch.stack([mu32, rs32], 1)
+    xa = xd.clone().requires_grad_()
+    if torch_ln:
+        ya = F.layer_norm(xa, (C,), g.to(D), b.to(D), e32)
+    else:
+        ma = xa.mean(1, keepdim=True)
+        ya = (xa - ma) / (((xa - ma) ** 2).mean(1, keepdim=True).sqrt() + e32) * g.to(D) + b.to(D)
+    (ya * dy.to(D)).sum().backward()
+    y = R.mgfn_ln_apply_ref(x, st64, g, b)
+    dx = R.mgfn_ln_bwd_ref(dy, x, st64, g, torch_ln, eps, add)
+    plain = [0, 3, 4]                              # torch's own float64 LayerNorm loses digits on the 1000 + noise row (its variance cancels): 1e-5 there
+    assert close(y[0][plain], ya.detach()[plain]) and close(y[0][1], ya.detach()[1], 1e-5)
+    assert close((dx[0] - add.to(D))[plain], xa.grad[plain], 1e-9) and close((dx[0] - add.to(D))[1], xa.grad[1], 1e-4)
+    assert torch.equal(y[0][2], b.to(D)), "constant row: y == b"
+    y = R.mgfn_ln_apply_ref(x, st32, g, b)
+    inside((x - st32[:, :1]) * st32[:, 1:] * g + b, y, "ln apply")
+    dx = R.mgfn_ln_bwd_ref(dy, x, st32, g, torch_ln, eps, add)
+    d32, xh32 = dy * g, (x - st32[:, :1]) * st32[:, 1:]
+    k32 = st32[:, 1:] if torch_ln else 1 / (1 / st32[:, 1:] - eps)
+    got = (d32 - d32.mean(1, keepdim=True)) * st32[:, 1:] - xh32 * ((d32 * xh32).mean(1, keepdim=True) * k32) + add
+    inside(got[keep], (dx[0][keep], dx[1][keep]), "ln bwd")
+    not_vacuous((dx[0][[0, 3, 4]], dx[1][[0, 3, 4]]), "ln bwd")
+    if torch_ln:
+        assert bool(torch.isfinite(dx[0]).all()) and bool(torch.isfinite(dx[1]).all())
+
+
+@pytest.mark.parametrize("M", [2, 129])
+@pytest.mark.parametrize("C", [4, 260])
+def test_mgfn_batchnorm_refs(M, C):
+    eps, mom = 1e-5, 0.1
+    x = synth_tensor(45, "bnx%d_%d" % (M, C), (M, C), -3, 5)
+    x[:, 1] = 2.5                                                       # a constant channel
+    g, b = synth_tensor(45, "bng", (C,), 0.5, 1.5), synth_tensor(45, "bnb", (C,), -0.2, 0.2)
+    rm, rv = synth_tensor(45, "bnrm", (C,), -0.1, 0.1), synth_tensor(45, "bnrv", (C,), 0.5, 1.5)
+    dy, add = synth_tensor(45, "bndy%d" % M, (M, C), -1, 1), synth_tensor(45, "bnad%d" % M, (M, C), -1, 1)
+
+    def run(dt):
+        bn = torch.nn.BatchNorm1d(C, eps=R.f32(eps), momentum=R.f32(mom)).to(dt).train()
+        with torch.no_grad():
+            bn.weight.copy_(g), bn.bias.copy_(b), bn.running_mean.copy_(rm), bn.running_var.copy_(rv)
+        xa = x.to(dt).clone().requires_grad_()
+        y = bn(xa)
+        (y * dy.to(dt)).sum().backward()
+        return y.detach(), bn.running_mean, bn.running_var, xa.grad, bn.weight.grad, bn.bias.grad
+    t64, t32 = run(D), run(F32T)
+    f = R.mgfn_bn_fwd_ref(x, g, b, eps, mom, rm, rv)
+    xd = x.to(D)
+    assert close(f["y"][0], t64[0]) and close(f["running_mean"][0], t64[1]) and close(f["running_var"][0], t64[2])
+    assert close(f["mean"][0], xd.mean(0)) and close(f["invstd"][0], 1 / (xd.var(0, unbiased=False) + R.f32(eps)).sqrt())
+    for key, got in (("y", t32[0]), ("running_mean", t32[1]), ("running_var", t32[2])):
+        inside(got, f[key], "bn " + key)
+        cols = f["invstd"][0] < 10                 # not the constant channel (nor, at M = 2, two close values): an invstd of up to 316 multiplies the error of the mean
+        assert int(cols.sum()) >= C // 2 and not bool(cols[1])
+        not_vacuous((f[key][0][..., cols], f[key][1][..., cols]), "bn " + key)
+    outside(R.mgfn_bn_fwd_ref(x, g, b, eps, mom, rm, rv, wrong="biased_running_var")["running_var"][0], f["running_var"], "a biased running_var")
+    assert R.mgfn_bn_fwd_ref(x, g, b, eps, mom)["running_var"] is None
+    one = R.mgfn_bn_fwd_ref(x[:1], g, b, eps, mom, rm, rv)               # M = 1: the biased variance, 0
+    assert close(one["running_var"][0], (1 - R.f32(mom)) * rv.to(D)) and close(one["y"][0], b.to(D).expand(1, C))
+    stat64 = torch.cat([f["mean"][0], f["invstd"][0]])
+    bw = R.mgfn_bn_bwd_ref(dy, x, stat64, g, add)
+    assert float((bw["dx"][0] - add.to(D) - t64[3]).abs().max()) <= 1e-9 * float(t64[3].abs().max() + 1)
+    assert float((bw["dgamma"][0] - t64[4]).abs().max()) <= 1e-9 * float(t64[4].abs().max() + 1) and close(bw["dbeta"][0], t64[5])
+    mean32 = x.mean(0)
+    stat32 = torch.cat([mean32, 1 / (x.var(0, unbiased=False) + eps).sqrt()])
+    bw = R.mgfn_bn_bwd_ref(dy, x, stat32, g, add)
+    xh = (x - stat32[:C]) * stat32[C:]
+    dbe, dga = dy.sum(0), (dy * xh).sum(0)
+    inside(dbe, bw["dbeta"], "bn dbeta")
+    inside(dga, bw["dgamma"], "bn dgamma")
+    inside(g * stat32[C:] * (dy - dbe / M - xh * dga / M) + add, bw["dx"], "bn dx")
+    not_vacuous(bw["dx"], "bn dx", 1e-2)                                 # the constant channel: invstd = 316, the bound grows with it
+
+
+@pytest.mark.parametrize("C", R.MGFN_ROW_C)
+def test_mgfn_head_refs(C):
+    M, eps = 5, 1e-5
+    x = _hard_rows(synth_tensor(46, "hx%d" % C, (M, C), -3, 5))
+    lw, lb = synth_tensor(46, "hlw%d" % C, (C,), 0.5, 1.5), synth_tensor(46, "hlb%d" % C, (C,), -0.1, 0.1)
+    fw = synth_tensor(46, "hfw%d" % C, (C,), -0.5, 0.5)
+    dsc, dh = synth_tensor(46, "hds%d" % C, (M,), -1, 1), synth_tensor(46, "hdh%d" % C, (M, C), -1, 1)
+    for fb in (0.05, 100.0, -100.0):
+        def run(dt):
+            h = F.layer_norm(x.to(dt), (C,), lw.to(dt), lb.to(dt), R.f32(eps)).requires_grad_()
+            z = h @ fw.to(dt) + R.f32(fb)
+            s = torch.sigmoid(z)
+            (s * dsc.to(dt)).sum().backward()
+            return h.detach(), z.detach(), s.detach(), h.detach().norm(dim=1), h.grad
+        t64, t32 = run(D), run(F32T)
+        r = R.mgfn_head_ref(x, lw, lb, fw, fb, eps)
+        for i, key in enumerate(("h", "logit", "score", "mag")):
+            assert close(r[key][0], t64[i]), key
+            inside(t32[i], r[key], "head " + key)
+        not_vacuous((r["h"][0][[0, 3, 4]], r["h"][1][[0, 3, 4]]), "head h")
+        (o64, _), (z64, _) = R.mgfn_head_bwd_ref(t64[2], dsc, fw, dh)
+        assert float((o64 - dh.to(D) - t64[4]).abs().max()) <= 1e-12
+        if abs(fb) == 100.0 and C > 4:             # saturated: float64 gives exactly 1, or a value below the smallest normal fp32 (the kernel's expf overflows: exactly 0)
+            assert bool(((r["score"][0] == 1.0) | (r["score"][0] < R.FLOOR32)).all())
+        ob, zb = R.mgfn_head_bwd_ref(t32[2], dsc, fw, dh)
+        z32 = dsc * t32[2] * (1 - t32[2])
+        inside(z32, zb, "head_bwd dz")
+        inside(dh + fw * z32[:, None], ob, "head_bwd dh")
+        not_vacuous(ob, "head_bwd dh")
+
+
+def test_mgfn_gelu_refs():
+    hard = torch.tensor([0.0, -0.0, 2.0 ** -140, -2.0 ** -140, 1e-3, -1e-3, 0.7, -0.7, 3, -3, 6, -6, 10, -10, 40, -40], dtype=F32T)
+    x = torch.cat([hard, synth_tensor(47, "gelux", (1012,), -6, 6)])
+    dy = synth_tensor(47, "geludy", (1028,), -1, 1)
+
+    def run(dt):
+        xa = x.to(dt).clone().requires_grad_()
+        y = F.gelu(xa)
+        (y * dy.to(dt)).sum().backward()
+        return y.detach(), xa.grad
+    t64, t32 = run(D), run(F32T)
+    y, dx = R.mgfn_gelu_ref(x), R.mgfn_gelu_bwd_ref(x, dy)
+    assert close(y[0], t64[0]) and close(dx[0], t64[1])
+    inside(t32[0], y, "gelu")
+    # backward: the formula in fp32 torch ops (torch.erf, torch.exp: the functions the constants were measured on). torch's own fp32 GELU backward on the CPU
+    # uses a vectorised erf with an ABSOLUTE error of a few 2^-24 (5.4 * 2^-24 of the result at x = 0.006), which no relative constant describes
+    xf = x.clone()
+    inside(dy * (0.5 * (1 + torch.erf(xf * 0.70710678118654752440)) + xf * 0.39894228040143267794 * torch.exp(-0.5 * xf * xf)), dx, "gelu bwd")
+    assert float((t32[1].double() - dx[0]).abs().max()) <= 8 * U
+    not_vacuous(y, "gelu", 1e-5)
+    not_vacuous(dx, "gelu bwd", 1e-5)
+    assert float(y[0][15]) == 0.0 and bool(torch.signbit(y[0][15])) and float(y[0][12]) == 10.0 and float(y[0][14]) == 40.0       # the tails float64 rounds to 0 / x
+    assert float(dx[0][15]) == 0.0 and float(dx[0][14]) == float(dy[14])
+
+
+def test_mgfn_reduction_refs():
+    C = 65
+    for M in (127, 129, 385):
+        a, x = synth_tensor(48, "cra%d" % M, (M, C), -1, 1), synth_tensor(48, "crx%d" % M, (M, C), -3, 5)
+        st_row = torch.stack([x.mean(1), 1 / (x.var(1, unbiased=False) + 1e-5).sqrt()], 1)
+        st_col = torch.cat([x.mean(0), 1 / (x.var(0, unbiased=False) + 1e-5).sqrt()])
+        rowf = synth_tensor(48, "crr%d" % M, (M,), -1, 1)
+        cases = {0: (None, None), 1: (x, st_row), 2: (x, st_col), 3: (None, st_col), 4: (None, rowf)}
+        for mode, (xx, st) in cases.items():
+            for dt in (D, F32T):
+                ad = a.to(dt)
+                if mode == 0:
+                    o0, o1 = ad.sum(0), torch.zeros(C, dtype=dt)
+                elif mode == 1:
+                    o0, o1 = ad.sum(0), (ad * ((xx.to(dt) - st[:, :1].to(dt)) * st[:, 1:].to(dt))).sum(0)
+                elif mode == 2:
+                    o0, o1 = ad.sum(0), (ad * ((xx.to(dt) - st[:C].to(dt)) * st[C:].to(dt))).sum(0)
+                elif mode == 3:
+                    o0, o1 = ((ad - st[:C].to(dt)) ** 2).sum(0), torch.zeros(C, dtype=dt)
+                else:
+                    o0, o1 = (st.to(dt)[:, None] * ad).sum(0), st.to(dt).sum().expand(C)
+                r0, r1 = R.mgfn_col_reduce_ref(a, mode, 0.5, xx, st)
+                if dt == D:
+                    assert float((r0[0] - 0.5 * o0).abs().max()) <= 1e-12 * M and float((r1[0] - 0.5 * o1).abs().max()) <= 1e-12 * M
+                else:
+                    inside(0.5 * o0, r0, "col_reduce mode %d out0" % mode)
+                    inside(0.5 * o1, r1, "col_reduce mode %d out1" % mode)
+                    assert float(r0[1].max()) <= 1e-3 * M and float(r1[1].max()) <= 1e-3 * M
+            if M % R.MT_CHUNK:
+                w0, w1 = R.mgfn_col_reduce_ref(a, mode, 0.5, xx, st, wrong="skip_last_chunk")
+                outside(w0[0], r0, "a column reduction that skips the last partial chunk (mode %d)" % mode)
+        m0, _ = R.mgfn_col_reduce_ref(a, 3, 1.0, None, None)
+        assert torch.equal(m0[0], R.mgfn_col_reduce_ref(a, 0, 1.0)[0][0])          # mode 3 with st == NULL is mode 0
+    sc = synth_tensor(48, "cm", (10 * (1 + 256 + 257),), 0, 1)
+    seg = [0, 1, 257, 514]
+    cm = R.mgfn_crop_mean_ref(sc, seg, 10)
+    want = torch.cat([sc[10 * seg[v]:10 * seg[v + 1]].view(10, -1).to(D).mean(0) for v in range(3)])
+    assert close(cm[0], want)
+    inside(torch.cat([sc[10 * seg[v]:10 * seg[v + 1]].view(10, -1).mean(0) for v in range(3)]), cm, "crop_mean")
+    not_vacuous(cm, "crop_mean", 1e-5)
+
+
+@pytest.mark.parametrize("M", [17, 129, 300])
+def test_mgfn_transpose_and_wgrad_refs(M):
+    taps, C, N = 3, 16, 64
+    lengths = R.gemm_lengths(M)
+    off, bounds = R.mgfn_ragged(lengths)
+    ldk = (M + 15) // 16 * 16
+    x, dy = synth_tensor(49, "wgx%d" % M, (M, C), -2, 2), synth_tensor(49, "wgd%d" % M, (M, N), -1, 1)
+    at, dyt = R.mgfn_transpose_ref(x, bounds, taps, ldk), R.mgfn_transpose_ref(dy, None, 1, ldk)
+    assert at.shape == (taps * C, ldk) and float(at[:, M:].abs().max() if ldk > M else 0) == 0 and torch.equal(dyt[:, :M], dy.to(D).t())
+    for m in (0, M // 2, M - 1):
+        for t in range(taps):
+            src = m + t - 1
+            want = x[src].to(D) if bounds[m, 0] <= src < bounds[m, 1] else torch.zeros(C, dtype=D)
+            assert torch.equal(at[t * C:(t + 1) * C, m], want)
+    w = torch.zeros((N, taps, C), dtype=D, requires_grad=True)
+    (_conv_tokens(x.to(D), off, w, None, taps) * dy.to(D)).sum().backward()
+    rb = R.mgfn_wgrad_ref(at, dyt)
+    assert close(rb[0], w.grad.reshape(N, taps * C).t(), 1e-10)
+    inside(at.float() @ dyt.float().t(), rb, "wgrad")
+    not_vacuous(rb, "wgrad")
+    assert R.mgfn_wgrad_slices(ldk, taps * C, N)[1] == (1 if M <= 128 else 2 if M == 129 else 3)
