@@ -596,6 +596,36 @@ int32_t tedspad_clip_augment(const void *blob_host, void *blob_dev, int64_t blob
                              int64_t luts_off, int32_t nluts, float *out, int64_t out_elems, int32_t oh, int32_t ow, int64_t so_c, int64_t so_h,
                              int64_t so_w, void *stream);
 
+/* The validation loaders' frames (aux_code/ucf101_dl.py: single_val_dataloader.augmentation :297-320, contrastive_val_dataloader.augmentation :873-896) for a
+ * whole batch in ONE launch: uint8 (H,W,3) frame -> center_crop (torchvision zero-pads where the crop is larger than the frame, so the box origin may be
+ * NEGATIVE and every source coordinate outside [0,H) x [0,W) is zero) -> Pillow's two-pass BILINEAR resize as in tedspad_clip_augment -> hflip -> / 255.
+ * The blob is {nrec records | int32 Pillow tables}, laid out, uploaded and checked like tedspad_clip_augment's; a table's windows must not move backwards from
+ * one output row to the next. A workgroup owns `band` output rows of three planes: it resamples every temporary row the band's vertical taps reach ONCE into
+ * LDS (bytes), then runs the vertical pass out of LDS, so no frame-sized buffer limits oh x ow. The caller picks `band` (1 .. tedspad_val_clips_band_max());
+ * over the worst record and band the temporary rows (3 planes x ow bytes each), plus in the activation form the band's 16-bit output rows, must fit
+ * tedspad_val_clips_lds_bytes(): otherwise TEDSPAD_EUNSUPPORTED and nothing is launched (ted_spad_amd/val_clips.band_height picks the largest that fits).
+ *   tedspad_val_clips      fp32 out[dst + c*so_c + y*so_h + x*so_w], the three planes of a workgroup are the colours of one record.
+ *   tedspad_val_clips_act  the anonymizer's input for the pseudo-images the training / validation loops feed it: the nrec = B*n records are n per
+ *                          batch item; with p = c*n + k (colour c of record k of item b) image b*n + p/3 of the 16-bit channels-last activation
+ *                          (nrec, oh, ow*cpad/8) x 16 bytes holds plane p in channel p%3, the other channels zero (cpad 4: pixel pairs, even ow; cpad 8),
+ *                          bit-identical to tedspad_clip_to_channels_last of the permuted fp32 batch. `dst` must be 0.
+ * Flags: TEDSPAD_AUG_HFLIP and TEDSPAD_AUG_REVERSE only. Bit-exact with Pillow (tests/test_hip_val_clips.py). */
+typedef struct tedspad_val_record {
+    const uint8_t *src;                 /* the (H, W, 3) uint8 source frame */
+    int64_t dst;                        /* fp32 form: element offset of the output frame in `out` */
+    int32_t H, W;
+    int32_t top, left, ch, cw;          /* crop box in frame coordinates; it may leave the frame on every side (zero fill) but must intersect it */
+    int32_t ytab, xtab, ytaps, xtaps;   /* the two tables (crop height -> oh, crop width -> ow): word offsets and taps per row */
+    int32_t flags;                      /* TEDSPAD_AUG_HFLIP | TEDSPAD_AUG_REVERSE */
+    int32_t reserved;                   /* 0 */
+} tedspad_val_record;
+int32_t tedspad_val_clips_lds_bytes(void);
+int32_t tedspad_val_clips_band_max(void);
+int32_t tedspad_val_clips(const void *blob_host, void *blob_dev, int64_t blob_bytes, int32_t nrec, int64_t tables_off, int64_t table_words, float *out,
+                          int64_t out_elems, int32_t oh, int32_t ow, int32_t band, int64_t so_c, int64_t so_h, int64_t so_w, void *stream);
+int32_t tedspad_val_clips_act(const void *blob_host, void *blob_dev, int64_t blob_bytes, int32_t nrec, int64_t tables_off, int64_t table_words, void *act,
+                              int64_t act_bytes, int32_t n, int32_t oh, int32_t ow, int32_t band, int32_t cpad, int32_t dtype, void *stream);
+
 /* The VISPR loaders' per-image augmentation (aux_code/vispr_dl.py: vispr_dataset.augmentation :71-129, vispr_ssl_dataset.augmentation :186-251) for a whole
  * ragged batch in ONE launch: contiguous uint8 (3,H,W) image (torchvision.io.read_image's layout) -> resized_crop (crop, zero-filled right of and below the
  * image, + ATen's antialiased bilinear resize on fp32: width pass, height pass, one rounding half to even) -> contrast / hue / saturation / brightness /

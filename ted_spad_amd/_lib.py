@@ -124,6 +124,10 @@ SYMBOLS = {
     "tedspad_frames_crop_resize_act": (_I32, [_P] + [_I32] * 16 + [_P, _P, C.c_float, _I32, _P] + [_I32] * 2 + [_P]),
     "tedspad_frames_crop_resize_pil_act": (_I32, [_P] + [_I32] * 15 + [_P, _I32, _P, _I32, _P] + [_I32] * 2 + [_P]),
     "tedspad_clip_augment": (_I32, [_P, _P, _I64, _I32, _I64, _I64, _I64, _I32, _P, _I64, _I32, _I32, _I64, _I64, _I64, _P]),
+    "tedspad_val_clips_lds_bytes": (_I32, []),
+    "tedspad_val_clips_band_max": (_I32, []),
+    "tedspad_val_clips": (_I32, [_P, _P, _I64, _I32, _I64, _I64, _P, _I64, _I32, _I32, _I32, _I64, _I64, _I64, _P]),
+    "tedspad_val_clips_act": (_I32, [_P, _P, _I64, _I32, _I64, _I64, _P, _I64, _I32, _I32, _I32, _I32, _I32, _I32, _P]),
     "tedspad_image_augment": (_I32, [_P, _P, _I64, _I32, _I64, _I64, _I64, _I32, _P, _I64, _P, _I64, _I32, _I32, _I64, _I64, _I64, _P]),
     "tedspad_segment_pool_mag":(_I32, [_P, _I32, _I32, _I32, _I32, _P, _P]),
     "tedspad_count_saturated": (_I32, [_P, _I64, _I32, _I32, _I32, _P, _P]),

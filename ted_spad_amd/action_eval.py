@@ -4,6 +4,8 @@
                                                                         train_anonymizer.py:227-272) / `val_epoch`
                                                                         (action_training/train_anonymized_action.py:126-169; with
                                                                         fa_model=None, train_action.py:119-152)
+    ActionValidator.evaluate_frames(videos, records, labels, paths, reso)   the same batch from decoded uint8 frames (val_clips.py): with an
+                                                                        anonymizer one launch writes its 16-bit input, no fp32 batch
     ActionValidator.end_pass()                                          the end of one (mode, cropping_fac) pass: the two numbers
                                                                         `val_epoch*` returns and the "Running Avg Accuracy" line
                                                                         (train_anonymizer.py:281-301,475-488)
@@ -135,7 +137,6 @@ class ActionValidator:
         """inputs_video: (B, T, 3, H, W) fp32 cuda as the loader delivers it (T = num_frames, or 3 x num_frames for the triplet loaders);
         labels: (B) class indices (list / numpy / tensor); vid_paths: B paths. Returns dict(logits, probs, loss, pred) of device tensors."""
         require_cuda(inputs_video, "ActionValidator.evaluate")
-        p = self.params
         vid_paths = list(vid_paths)
         if len(vid_paths) != inputs_video.shape[0]:
             raise ValueError("ActionValidator.evaluate: %d paths for a batch of %d" % (len(vid_paths), inputs_video.shape[0]))
@@ -147,6 +148,34 @@ class ActionValidator:
                 clip = self.fa(frames).reshape(shape)                 # :243
             else:
                 clip = inputs_video.permute(0, 2, 1, 3, 4)            # train_action.py:120
+        return self._evaluate_clip(clip, labels, vid_paths)
+
+    def evaluate_frames(self, videos, records, labels, vid_paths, reso):
+        """The same batch from DECODED FRAMES: videos / records / reso as `val_clips.val_clips` takes them (records[b]: the 16 or 3 x 16 frame records
+        of sample b, `val_clips.sample_val_*`). With an anonymizer ONE launch (val_clips.val_clips_act) writes the 16-bit activation of the pseudo-images
+        its first conv reads (Q2) and `fa.forward_act` starts there: the fp32 batch and `_feed`'s permuted copy are never written, and the logits are those
+        of `evaluate(val_clips.val_clips(videos, records, reso), ...)` bit for bit. Without one the fp32 batch is written and `evaluate` runs on it."""
+        from . import val_clips
+        if self.fa is None:
+            return self.evaluate(val_clips.val_clips(videos, records, reso), labels, vid_paths)
+        if not hasattr(self.fa, "forward_act"):
+            raise TypeError("ActionValidator.evaluate_frames: fa_model %s has no forward_act (UnetPlusPlus and UNet start from the 16-bit activation)"
+                            % type(self.fa).__name__)
+        vid_paths = list(vid_paths)
+        if len(vid_paths) != len(records):
+            raise ValueError("ActionValidator.evaluate_frames: %d paths for a batch of %d" % (len(vid_paths), len(records)))
+        self.ft.eval()
+        self.fa.eval()
+        with torch.no_grad():
+            act = val_clips.val_clips_act(videos, records, reso, self.fa.ACT_CPAD, self.fa.compute_dtype)
+            b, t = len(records), len(records[0])
+            clip = self.fa.forward_act(act).reshape(b, 3, t, int(reso[0]), int(reso[1]))      # :243 (the Q2 reshape back)
+        return self._evaluate_clip(clip, labels, vid_paths)
+
+    def _evaluate_clip(self, clip, labels, vid_paths):
+        """clip (B, 3, T, H, W) as ft sees it -> the heads, the losses and the votes (:246-294)."""
+        p = self.params
+        with torch.no_grad():
             t = clip.shape[2]
             if t == 3 * p.num_frames:
                 clips = torch.split(clip, [p.num_frames] * 3, dim=2)  # :246

@@ -114,6 +114,15 @@ __device__ __forceinline__ uint4 pack8_lim(const float (&f)[8], float lim) {
     return make_uint4(w[0], w[1], w[2], w[3]);
 }
 
+// one pixel's channels (v[c], c < 8, zero from C on) rounded to T at pixel slot `ox` of a 16-bit LDS row of a network's input activation
+// (cpad 4: pixel pairs {c0 c1 c2 0 | c0 c1 c2 0}, cpad 8: {c0 c1 c2 0 0 0 0 0}; feed.hip, val_clips.hip)
+template <typename T>
+__device__ __forceinline__ void act_put_pixel(unsigned char *tile, int cpad, int ox, const float (&v)[8]) {
+    const uint4 pk = pack8<T>(v);
+    if (cpad == 4) reinterpret_cast<uint2 *>(tile)[ox] = make_uint2(pk.x, pk.y);
+    else reinterpret_cast<uint4 *>(tile)[ox] = pk;
+}
+
 template <typename T>
 __device__ __forceinline__ uint4 pk_max8(uint4 a, uint4 b) {
     return make_uint4(T::pk_max(a.x, b.x), T::pk_max(a.y, b.y), T::pk_max(a.z, b.z), T::pk_max(a.w, b.w));

@@ -328,14 +328,6 @@ __device__ __forceinline__ long act_src_frame(const ActOutKP &a, int fo, int T) 
     return fr >= 0 && fr < T ? fr : -1;
 }
 
-// one pixel's channels (v[c], c < 8, zero from C on) rounded to T at pixel slot `ox` of the 16-bit LDS row
-template <typename T>
-__device__ __forceinline__ void act_put_pixel(unsigned char *tile, int cpad, int ox, const float (&v)[8]) {
-    const uint4 pk = pack8<T>(v);
-    if (cpad == 4) reinterpret_cast<uint2 *>(tile)[ox] = make_uint2(pk.x, pk.y);
-    else reinterpret_cast<uint4 *>(tile)[ox] = pk;
-}
-
 // row `orow` (= frame * oh + y) of the activation: `n16` 16-byte pieces from the LDS row, or zeros
 __device__ __forceinline__ void act_store_row(const ActOutKP &a, long orow, int n16, const unsigned char *tile) {
     uint4 *dst = a.act + orow * n16;
