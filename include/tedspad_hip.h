@@ -174,6 +174,22 @@ int32_t tedspad_bneck_tail_fwd(const tedspad_conv_desc *d2, const void *x, const
                                const void *w3p, const float *scale3, const float *shift3, int32_t cout3, const void *residual, int32_t ldres,
                                const void *x2, int32_t ldx2, const float *scale_d, void *y, int32_t ldy, int32_t relu, int32_t variant, void *stream);
 
+/* The plain block's tail above AND the next block's conv1 in one launch (csrc/conv_bneck_fold.hip) -- replaces, for two consecutive layer1
+ * bottlenecks on four-frame clips, the tail of the first `Bottleneck.forward` and the head of the second (aux_code/models/large_i3d.py:61-84:
+ * lines 69-84 of block i, then lines 61-68 of block i + 1):
+ *     y      = act( bn3(conv3(relu(bn2(conv2(x))))) + residual )        bit-identical to tedspad_bneck_tail_fwd's
+ *     h_next = relu( bn1'(conv1'(y)) )                                  conv1' 3x1x1, stride 1, pads (1,0,0), 256 -> 64
+ * so that `y` is not read a third time only to make the 64-channel h_next. d2 as above with t == 4, a 1 x 3 x 3 kernel and pads (0,1,1),
+ * any h and w: a workgroup owns an 8 x 8 pixel patch (partial at the right / bottom edge) across the four frames of a clip, one frame per wave, and the temporal
+ * neighbours of a pixel are read from the sibling waves' LDS row images. cout3 is 256; w3p as above (64 columns).
+ * `w1p` is [4][3][64][64] 16-bit: tile (g, dt) = conv1' weights of output channels 0..63 (rows) against input channels 64 g .. 64 g + 63 at
+ * temporal tap dt; the columns of the dt = 1 tiles are in the accumulator k order of w3p, those of dt = 0 and 2 in natural order.
+ * scale1 / shift1: bn1' folded, 64 floats each. h_next is (n,4,h,w,ldh). */
+int32_t tedspad_bneck_tail_fold_fwd(const tedspad_conv_desc *d2, const void *x, const void *w2_packed, const float *scale2, const float *shift2,
+                                    const void *w3p, const float *scale3, const float *shift3, const void *residual, int32_t ldres, void *y,
+                                    int32_t ldy, int32_t relu, const void *w1p, const float *scale1, const float *shift1, void *h_next, int32_t ldh,
+                                    void *stream);
+
 /* WHOLE bottleneck of a plain I3Res50 layer3 block (csrc/conv_bneck_frame.hip) -- replaces the `Bottleneck.forward` of
  * aux_code/models/large_i3d.py:61-84 for blocks without `downsample` on 14 x 14 frames (cin = 1024, cmid = 256):
  *     y = act( bn3(conv3( relu(bn2(conv2( relu(bn1(conv1(x))) ))) )) + x )

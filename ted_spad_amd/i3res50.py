@@ -106,6 +106,11 @@ class I3Res50(nn.Module):
                             s3, b3 = self._bn_fold(blk.bn3)
                             P[p + "dual"] = E.PackedConv.fused_pair(blk.conv3.weight, s3, b3, blk.downsample[0].weight, s, b,
                                                                     dtype=self.compute_dtype, device=dev)
+            for i in range(len(self.layer1) - 1):               # a plain layer1 tail that also emits the next block's conv1 (four-frame clips)
+                p, q = "layer1.%d." % i, "layer1.%d." % (i + 1)
+                w1 = self.layer1[i + 1].conv1.weight
+                if (p + "tail") in P and E.BneckTailFold.supported(P[p + "tail"], w1):
+                    P[p + "fold"] = E.BneckTailFold(P[p + "tail"], P[q + "conv1"], w1)
             self._packed, self._packed_sig = P, sig
         return self._packed
 
@@ -158,7 +163,7 @@ class I3Res50(nn.Module):
             taps["maxpool1"] = a
         if self.check_saturation:
             self._sat = E.count_saturated(a, self._sat)
-        pooled = False
+        pooled, h_next = False, None
         for li in range(1, 5):
             if li == 2 and not pooled:
                 a = E.maxpool(a, (2, 1, 1), (2, 1, 1))                   # large_i3d.py:139
@@ -170,7 +175,9 @@ class I3Res50(nn.Module):
                     a = bf(a)                                             # conv1 -> conv2 -> conv3 + residual: only the block input and output touch HBM
                     continue
                 tp = P.get(p + "conv1_tp") if taps is None else None
-                if tp is not None and tp.applies(a, (blk.temp_conv, 0, 0)):
+                if h_next is not None:
+                    h, h_next = h_next, None                              # conv1 + bn1 + ReLU came out of the previous block's tail (BneckTailFold)
+                elif tp is not None and tp.applies(a, (blk.temp_conv, 0, 0)):
                     h = tp(a)                                             # two frames: both outputs from ONE K = 2*cin GEMM, no products on zero padding
                 else:
                     h = P[p + "conv1"](a, pads=(blk.temp_conv, 0, 0))
@@ -182,8 +189,11 @@ class I3Res50(nn.Module):
                     # conv2 + bn2 + ReLU + conv3 + bn3 + (residual | downsample branch) + ReLU in one launch: the 64-channel tensor between
                     # the two convolutions is never written (large_i3d.py:69-84); the last block of layer1 pools over frame pairs as
                     # well (maxpool2, large_i3d.py:139)
+                    fold = P.get(p + "fold") if not fuse_pool else None
                     if tail.dual:
                         a = tail(h, pads=(0, 1, 1), x2=a)
+                    elif fold is not None and fold.applies(h, (0, 1, 1), a):
+                        a, h_next = fold(h, residual=a)                  # ... and the next block's conv1 (3x1x1) + bn1 + ReLU: the block output is not read for it again
                     else:
                         a = tail(h, pads=(0, 1, 1), residual=a, pool_t2=fuse_pool)
                         pooled = pooled or fuse_pool
