@@ -190,6 +190,16 @@ int32_t tedspad_bneck_tail_fold_fwd(const tedspad_conv_desc *d2, const void *x, 
                                     int32_t ldy, int32_t relu, const void *w1p, const float *scale1, const float *shift1, void *h_next, int32_t ldh,
                                     void *stream);
 
+/* The same for a block WITH the downsample branch, layer1.0 -> layer1.1's conv1 (csrc/conv_bneck_fold_dual.hip; large_i3d.py:49-54 in place of the residual):
+ *     y      = act( bn3(conv3(relu(bn2(conv2(x))))) + bn_d(conv_d(x2)) )     bit-identical to tedspad_bneck_tail_fwd's two-source form
+ *     h_next = relu( bn1'(conv1'(y)) )
+ * x2 is (n,4,h,w,ldx2) with 64 channels, w3p is the two-source image of tedspad_bneck_tail_fwd ([256][128]: conv3 columns in accumulator k order, then the
+ * downsample columns in natural order), shift3 holds b3 + bd and scale_d the downsample BatchNorm's scale (256 floats). Everything else as above. */
+int32_t tedspad_bneck_tail_fold2_fwd(const tedspad_conv_desc *d2, const void *x, const void *w2_packed, const float *scale2, const float *shift2,
+                                     const void *w3p, const float *scale3, const float *shift3, const void *x2, int32_t ldx2, const float *scale_d, void *y,
+                                     int32_t ldy, int32_t relu, const void *w1p, const float *scale1, const float *shift1, void *h_next, int32_t ldh,
+                                     void *stream);
+
 /* WHOLE bottleneck of a plain I3Res50 layer3 block (csrc/conv_bneck_frame.hip) -- replaces the `Bottleneck.forward` of
  * aux_code/models/large_i3d.py:61-84 for blocks without `downsample` on 14 x 14 frames (cin = 1024, cmid = 256):
  *     y = act( bn3(conv3( relu(bn2(conv2( relu(bn1(conv1(x))) ))) )) + x )

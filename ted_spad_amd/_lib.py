@@ -100,6 +100,7 @@ SYMBOLS = {
     "tedspad_deterministic_giveups": (_I32, []),
     "tedspad_bneck_tail_fwd": (_I32, [C.POINTER(ConvDesc)] + [_P] * 7 + [_I32, _P, _I32, _P, _I32, _P, _P, _I32, _I32, _I32, _P]),
     "tedspad_bneck_tail_fold_fwd": (_I32, [C.POINTER(ConvDesc)] + [_P] * 8 + [_I32, _P, _I32, _I32, _P, _P, _P, _P, _I32, _P]),
+    "tedspad_bneck_tail_fold2_fwd": (_I32, [C.POINTER(ConvDesc)] + [_P] * 8 + [_I32, _P, _P, _I32, _I32, _P, _P, _P, _P, _I32, _P]),
     "tedspad_clip_to_tp": (_I32, [_P, _P] + [_I32] * 5 + [_I64] * 5 + [_I32] * 4 + [_P]),
     "tedspad_stem_pt_wimg_bytes": (_I32, []),
     "tedspad_stem_pt_wimg16_bytes": (_I32, []),

@@ -475,13 +475,8 @@ __global__ __launch_bounds__(256, 2) void conv_bneck_tail_kernel(const BneckKP p
                         for (int h = 0; h < 2; ++h) {
                             const int r = 4 * q + 2 * h;
                             if (DUAL) {
-                                float v[2];
-#pragma unroll
-                                for (int e = 0; e < 2; ++e) {
-                                    const float o = a3[b][r + e] * s3[q][2 * h + e] + b3[q][2 * h + e] + ad[b][r + e] * sd[q][2 * h + e];
-                                    v[e] = p.relu ? __builtin_fmaxf(o, 0.f) : o;
-                                }
-                                d[tt][b][q][h] = (unsigned)T::from_f32(v[0]) | ((unsigned)T::from_f32(v[1]) << 16);
+                                d[tt][b][q][h] = tail_pair_dual<T>(a3[b][r], a3[b][r + 1], s3[q][2 * h], s3[q][2 * h + 1], b3[q][2 * h], b3[q][2 * h + 1],
+                                                                   ad[b][r], ad[b][r + 1], sd[q][2 * h], sd[q][2 * h + 1], p.relu);
                             } else {
                                 // without a residual pointer rs is zero: the add stays (no select per value)
                                 d[tt][b][q][h] = tail_pair<T, true>(a3[b][r], a3[b][r + 1], s3[q][2 * h], s3[q][2 * h + 1], b3[q][2 * h], b3[q][2 * h + 1], rs[q][h], lo);

@@ -58,6 +58,17 @@ constexpr int BK = 64;                  // K elements per LDS tile row (8 chunks
 constexpr int KTAB_MAX_BYTES = 10240;   // Kpad <= 10240 (one int2 per 8 K elements)
 constexpr int KTAB_SMALL_BYTES = 1024;  // "short-K" configs: Kpad <= 1024, smaller LDS -> 2-3 workgroups per CU
 
+// The two-source bottleneck tails (conv_bneck.hip, conv_bneck_fold_dual.hip): bn3(conv3) + bn_d(conv_d) (+ ReLU) of two neighbouring output channels -> one
+// packed pair; b0, b1 carry both shifts. ONE expression for both kernels, and the two fused multiply-adds written out: left to -ffp-contract=fast,
+// `a * s + b + d * sd` became fma(d, sd, fma(a, s, b)) in conv_bneck.hip and a packed multiply with two adds in the fold, a last-bit difference in y.
+template <typename T>
+__device__ __forceinline__ unsigned tail_pair_dual(float a0, float a1, float s0, float s1, float b0, float b1, float d0, float d1, float sd0, float sd1, int relu) {
+    const float o0 = __builtin_fmaf(d0, sd0, __builtin_fmaf(a0, s0, b0));
+    const float v0 = relu ? __builtin_fmaxf(o0, 0.f) : o0;
+    const float o1 = __builtin_fmaf(d1, sd1, __builtin_fmaf(a1, s1, b1));
+    const float v1 = relu ? __builtin_fmaxf(o1, 0.f) : o1;
+    return (unsigned)T::from_f32(v0) | ((unsigned)T::from_f32(v1) << 16);
+}
 
 // conv_pw.hip: persistent pointwise kernel for 1x1x1 stride-1 convolutions with cin = 64 / 128 (tile_cfg 19).
 int32_t launch_conv_pw(int dtype, const ConvKP &p, hipStream_t s, bool pool_t = false);

@@ -30,6 +30,7 @@ BNECK_TAIL = os.environ.get("TEDSPAD_BNECK_TAIL", "1") != "0"   # layer1: conv2 
 BNECK_TAIL128 = os.environ.get("TEDSPAD_BNECK_TAIL128", "1") != "0"   # layer2's plain blocks (128 mid channels) on the fused tail as well; 0: conv2 + conv3 launches (A/B)
 BNECK_TAIL_POOL = os.environ.get("TEDSPAD_BNECK_TAIL_POOL", "1") != "0"   # layer1's last block: the fused tail with maxpool2 inside; 0: conv2 + (conv3 + pool) launches (A/B)
 L1_FOLD = os.environ.get("TEDSPAD_L1_FOLD", "1") != "0"   # layer1 on four-frame clips: a plain block's tail also emits the next block's conv1 (BneckTailFold); 0: tail + temporal-conv launches (A/B)
+L1_FOLD_DUAL = os.environ.get("TEDSPAD_L1_FOLD_DUAL", "1") != "0"   # ... and so does layer1.0's downsample tail (BneckTailFoldDual; needs L1_FOLD); 0: the two-source tail + the temporal-conv launch (A/B)
 TPAIR_MIN_COUT =int(os.environ.get("TEDSPAD_TPAIR_MIN_COUT", "128"))   # smallest cout that takes the folded form (256: layer2's 128-channel temporal convs stay on the temporal chunk-major tile)
 TPAIR = os.environ.get("TEDSPAD_TPAIR", "1") != "0"   # 3x1x1 convs on two-frame tensors as one K = 2*cin GEMM over both frames (TPairConv); 0: K = 3*cin with zero taps (A/B)
 STEM_POOL = os.environ.get("TEDSPAD_STEM_POOL", "1") != "0"   # the spatial half of maxpool1 inside the stem kernel too (StemPT.conv_pool); 0: separate (1,3,3) max-pool (A/B)
@@ -839,8 +840,8 @@ class BneckTailFold:
     (csrc/conv_bneck_fold.hip; large_i3d.py:61-84): a workgroup owns an 8 x 8 patch (a partial one at the frame's right / bottom edge: layer1 is 55 x 55 at
     224 x 224 clips) across the four frames, one frame per wave, so the temporal neighbours
     of a pixel sit in sibling waves and the 256-channel block output is not read again only to make the next block's 64-channel h.
-    Returns (y, h_next); y is bit-identical to the BneckTail's. The two-source (downsample) tail has no folded form yet: its second source's fragments and
-    accumulators do not fit beside the fold's tile in the 256 registers that keep two workgroups on a CU."""
+    Returns (y, h_next); y is bit-identical to the BneckTail's. The two-source (downsample) tail has its own folded form, BneckTailFoldDual: this class
+    refuses it (`supported`)."""
 
     def __init__(self, tail: "BneckTail", conv1: "PackedConv", w1: torch.Tensor):
         """conv1: the next block's PackedConv (its folded scale / shift are used); w1: that conv's (64, 256, 3, 1, 1) weight."""
@@ -876,6 +877,50 @@ class BneckTailFold:
                                                      self.w1p.data_ptr(), self.conv1.scale.data_ptr(), self.conv1.shift.data_ptr(), out_h.ptr, out_h.ld,
                                                      _stream_ptr()),
               "tedspad_bneck_tail_fold_fwd")
+        return out, out_h
+
+
+class BneckTailFoldDual:
+    """layer1.0's two-source BneckTail (conv3 + bn3 + the downsample branch on x2) AND layer1.1's conv1 (3x1x1, pads (1,0,0), 256 -> 64) + bn1 + ReLU as ONE
+    launch on four-frame clips (csrc/conv_bneck_fold_dual.hip): BneckTailFold's tile and fold with the downsample branch in place of the residual. The wave's
+    LDS row image holds its frame's 64 channels of x2, fetched again for each of the four output groups (L2 hits), so the second source costs no registers
+    beside the fold's tile. Reuses the tail's w3p / scale3 / shift3 / scale_d and BneckTailFold's w1p layout. Returns (y, h_next); y is bit-identical to
+    the two-source BneckTail's. Runs when both TEDSPAD_L1_FOLD and TEDSPAD_L1_FOLD_DUAL are on."""
+
+    def __init__(self, tail: "BneckTail", conv1: "PackedConv", w1: torch.Tensor):
+        """conv1: the next block's PackedConv (its folded scale / shift are used); w1: that conv's (64, 256, 3, 1, 1) weight."""
+        assert self.supported(tail, w1)
+        dev = tail.conv2.device
+        self.tail, self.conv1 = tail, conv1
+        w = w1.detach().to(dev, torch.float32).reshape(64, 4, 64, 3).permute(1, 3, 0, 2).contiguous()      # [group][dt][co][k], as BneckTailFold's
+        w[:, 1] = w[:, 1][:, :, torch.tensor(BneckTail.PERM[:64], device=dev)]                                # dt = 0 tap: accumulator k order
+        self.w1p = w.to(tail.conv2.torch_dtype).contiguous()
+
+    @staticmethod
+    def supported(tail: "BneckTail", w1: torch.Tensor) -> bool:
+        return (tuple(w1.shape) == (64, 256, 3, 1, 1) and tail.cmid == 64 and tail.cout3 == 256 and tail.dual and tail.conv2.k == (1, 3, 3))
+
+    def applies(self, x: Act, pads, x2: Optional[Act] = None) -> bool:
+        n, t, h, w = x.dims
+        return (L1_FOLD and L1_FOLD_DUAL and t == 4 and tuple(pads) == (0, 1, 1) and x.buf.dtype == self.tail.conv2.torch_dtype == self.conv1.torch_dtype and
+                (x2 is None or x2.buf.dtype == x.buf.dtype) and self.tail.applies(x, pads))
+
+    def __call__(self, x: Act, x2: Act, pads=(0, 1, 1), relu=True, out: Optional[Act] = None, out_h: Optional[Act] = None):
+        n, t, h, w = x.dims
+        tl, c2 = self.tail, self.tail.conv2
+        assert self.applies(x, pads, x2) and x2.dims == x.dims and x2.c == 64
+        if out is None:
+            out = Act.empty(n, t, h, w, 256, c2.torch_dtype, x.buf.device)
+        if out_h is None:
+            out_h = Act.empty(n, t, h, w, 64, c2.torch_dtype, x.buf.device)
+        assert out.dims == x.dims and out.c == 256 and out_h.dims == x.dims and out_h.c == 64
+        assert n * t * h * w * max(x.ld, out.ld, out_h.ld, x2.ld) < MAX_ELEMS
+        d = c2._desc(n, t, h, w, x.ld, pads, (t, h, w), 64, 0, True)
+        check(_lib.lib().tedspad_bneck_tail_fold2_fwd(C.byref(d), x.ptr, c2.w.data_ptr(), c2.scale.data_ptr(), c2.shift.data_ptr(), tl.w3p.data_ptr(),
+                                                      tl.scale3.data_ptr(), tl.shift3.data_ptr(), x2.ptr, x2.ld, tl.scale_d.data_ptr(), out.ptr, out.ld,
+                                                      int(relu), self.w1p.data_ptr(), self.conv1.scale.data_ptr(), self.conv1.shift.data_ptr(), out_h.ptr,
+                                                      out_h.ld, _stream_ptr()),
+              "tedspad_bneck_tail_fold2_fwd")
         return out, out_h
 
 

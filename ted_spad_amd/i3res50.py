@@ -111,6 +111,8 @@ class I3Res50(nn.Module):
                 w1 = self.layer1[i + 1].conv1.weight
                 if (p + "tail") in P and E.BneckTailFold.supported(P[p + "tail"], w1):
                     P[p + "fold"] = E.BneckTailFold(P[p + "tail"], P[q + "conv1"], w1)
+                elif (p + "tail") in P and E.BneckTailFoldDual.supported(P[p + "tail"], w1):      # layer1.0: the downsample tail does the same
+                    P[p + "fold2"] = E.BneckTailFoldDual(P[p + "tail"], P[q + "conv1"], w1)
             self._packed, self._packed_sig = P, sig
         return self._packed
 
@@ -190,7 +192,10 @@ class I3Res50(nn.Module):
                     # the two convolutions is never written (large_i3d.py:69-84); the last block of layer1 pools over frame pairs as
                     # well (maxpool2, large_i3d.py:139)
                     fold = P.get(p + "fold") if not fuse_pool else None
-                    if tail.dual:
+                    fold2 = P.get(p + "fold2") if not fuse_pool else None
+                    if tail.dual and fold2 is not None and fold2.applies(h, (0, 1, 1), a):
+                        a, h_next = fold2(h, x2=a)                       # the downsample tail and the next block's conv1 + bn1 + ReLU (BneckTailFoldDual)
+                    elif tail.dual:
                         a = tail(h, pads=(0, 1, 1), x2=a)
                     elif fold is not None and fold.applies(h, (0, 1, 1), a):
                         a, h_next = fold(h, residual=a)                  # ... and the next block's conv1 (3x1x1) + bn1 + ReLU: the block output is not read for it again
