@@ -275,7 +275,9 @@ int32_t tedspad_stem_pt_pool_fwd(const void *x_tp, const void *w_img, const floa
  * strides sn, sc, st, sh, sw = 1, rows 16-byte aligned (w % 4 == 0, x and every stride multiples of 4 elements). The persistent workgroups build their halo
  * images from it themselves (register-staged 16-byte loads requested a whole patch ahead, converted to the 16-bit dtype on the way into LDS): the 9.6 MB
  * per clip of tedspad_clip_to_tp records are never written or read. Same arithmetic, same results as tedspad_clip_to_tp + tedspad_stem_pt_pool_fwd(variant 6).
- * w_img16: the tap-pair image; variant: bits 8..10 timing ablations only. */
+ * w_img16: the tap-pair image; variant bit 3: the loader waves deal their tasks per LANE (every load behind per-lane plane guards and address arithmetic) instead
+ * of one (frame, half) per WAVE with scalar guards and buffer loads -- same results, kept for A/B and as the fallback for row strides past the buffer loads' range
+ * (TEDSPAD_STEM_UNIFORM=0 sets the bit for every call); bits 8..10 timing ablations only. */
 int32_t tedspad_stem_pt_pool_clip_fwd(const float *x, int32_t n, int32_t c, int32_t t, int32_t h, int32_t w, int64_t sn, int64_t sc, int64_t st, int64_t sh,
                                       int64_t sw, int32_t pad_t, int32_t stride_t, int32_t t_pairs, const void *w_img16, const float *scale,
                                       const float *shift, void *y, void *side, int32_t hp, int32_t wp, int32_t ldy, int32_t nwg, int32_t variant,

@@ -191,8 +191,18 @@ __device__ __forceinline__ void stem_pt_phase16(const unsigned char *dsm, const 
 // 16 waves at 128 registers instead of 8 at 256 (LW = 8: one task per loader thread and region, as in the 8-wave form). On the record path (LW = 4) the loaders issue
 // the halo LDS-DMA and wait for it, and pool the rows. Measured (375 clips, isolated): fp32 clip 4 045 -> 3 880 us, records 3 450 -> 3 160 us; cfg2 bench +1.2 %.
 // What bounds the fp32 form either way is the VALU port the conversion (3 instructions per value pair) and the address arithmetic share with the MFMA issue.
-template <typename T, int NW, bool POOL, int MF = 32, bool DIRECT = false, int LW = 0>
+//
+// UNI (DIRECT, LW = 8): the loader tasks are dealt so that a WAVE holds one (frame f, half hs): loader wave pair j = (wave - NW) >> 1 owns (f, hs) = (j >> 1, j & 1), its
+// 128 lanes the (halo row, column quad) tasks (110 / 100 of them busy -- the same 440 / 400 of 512 lanes as in the per-lane deal above). The plane (frame slot, channel)
+// that load e fetches then is the same for every lane of the wave, and everything that hangs on it -- the temporal and the channel guard, the zero-weight rule of value 15,
+// the plane's offset -- is scalar arithmetic: the eight plane offsets are formed once before the patch loop, the guards once per patch and plane. A lane keeps its pixel
+// guard (once per task, not per load) and ONE 32-bit byte offset that no patch changes. The load is a raw buffer load: scalar base = patch + plane, the lane's offset in
+// voffset; a lane outside the frame carries an offset past the descriptor's range and reads zeros from the range check, a plane outside the clip takes the zero page as
+// its base (16 records: the one lane whose offset is 0 reads its zeros, every other lane is out of range). Eight loads per region and wave either way: the counted waits
+// of the loader loop stand. Same planes, same conversion, same LDS slots as the per-lane deal: identical results.
+template <typename T, int NW, bool POOL, int MF = 32, bool DIRECT = false, int LW = 0, bool UNI = false>
 __global__ __launch_bounds__(64 * (NW + LW)) void conv_stem_pt_kernel(const StemPT p) {
+    static_assert(!UNI || (DIRECT && LW == 8), "the wave-uniform task deal is built for the fp32-clip form with 8 loader waves");
     static_assert(MF == 32 || (MF == 16 && NW == 8 && POOL), "the 16x16x32 form is built for 8 waves with the pool fused");
     static_assert(!DIRECT || (MF == 16 && NW == 8 && POOL), "the fp32-clip loader is built for the production form");
     static_assert(LW == 0 || (MF == 16 && NW == 8 && POOL), "loader waves are built for the production forms");
@@ -469,18 +479,63 @@ __global__ __launch_bounds__(64 * (NW + LW)) void conv_stem_pt_kernel(const Stem
         return;
     }
     if (LW && DIRECT && wave >= NW) {
-        setup_tasks();
+        // UNI: the wave's eight planes live in the LANES of two registers (the workgroup's scalar registers are taken: three patches, the walk, the kernel's arguments):
+        // lane l holds plane e = l & 7 -- its byte offset from the patch base, and its frame slot (a slot past every clip where the clip lacks the channel or the tap its
+        // weight: the temporal guard then fails on every patch). Per patch and region ONE compare makes the eight temporal guards (a ballot: bit e), one v_readlane per
+        // load the plane's offset. uvo: the lane's own byte offset inside a plane
+        unsigned upo = 0;
+        int ufs = 0, uvo[2];
+        if constexpr (UNI) {
+            static_assert(NTK == 1, "one task per loader lane and region");
+            const int lw = wave - NW, f = lw >> 2, hs = (lw >> 1) & 1;
+            const int i = (lw & 1) * 64 + lane;
+            const int row = i / 10, q4c = i - row * 10;
+#pragma unroll
+            for (int par = 0; par < 2; ++par) {
+                const bool task = i < pt_rows(par) * 10;
+                const int hr = 2 * row + par;
+                drow[par][0] = (task ? hr : 4095) | (4 * q4c) << 12;      // (row 4095 is outside every clip: the pixel guard fails, nothing is written: ldst < 0)
+                ldst[par][0] = task ? pt_off(par) + f * pt_frame(par) + row * PT_ROWB + 2 * q4c * 32 + 16 * hs : -1;
+                uvo[par] = (hr * p.sHf + 4 * q4c) * 4;
+            }
+            const int e = lane & 7, v = 6 * f + 8 * hs + e, fs = v / 3, ch = v - 3 * fs;
+            ufs = ch < p.C && !(e == 7 && hs) ? fs : 1 << 30;             // value 15 of a position meets a zero weight
+            upo = (unsigned)(ch * p.sC + fs * p.sT) * 4u;                 // (the host keeps it below 2^32)
+        } else setup_tasks();
+        const int urec = (20 * p.sHf + 40) * 4;                          // bytes from a plane's patch base to the end of the halo's last column quad
+        auto issue_u = [&](int par, const Patch &q) {                     // par is a literal at every call site
+            const int tt0 = 4 * q.tp - p.pad_t, meta = drow[par][0];
+            const bool rowok = (unsigned)(q.ih0 + (meta & 4095)) < (unsigned)p.H && (unsigned)(2 * q.wo0 - 4 + ((meta >> 12) & 255)) < (unsigned)p.W;
+            const int vo = rowok ? uvo[par] : (int)0x80000000;            // past every descriptor's range (the host keeps urec below 2^31)
+            unsigned po = upo;
+            int fsl = ufs;
+            asm volatile("" : "+v"(po), "+v"(fsl));                       // or hipcc reads the lanes once, ahead of the patch loop, into scalar registers it does not have
+            const unsigned tok = (unsigned)__builtin_amdgcn_ballot_w64((unsigned)(tt0 + fsl) < (unsigned)p.T);
+#pragma unroll
+            for (int e = 0; e < 8; ++e) {
+                const bool ok = (tok >> e) & 1;
+                unsigned off = (unsigned)__builtin_amdgcn_readlane((int)po, e);
+                asm volatile("" : "+s"(off));                             // read in any case: hipcc otherwise branches around the v_readlane and the two adds, per load
+                const unsigned char *b = ok ? reinterpret_cast<const unsigned char *>(q.pf) + off : zero;
+                const auto rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned char *>(b), 0, ok ? urec : 16, 0x00020000);
+                stage[par][0][e] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, vo, 0, 0));
+            }
+            asm volatile("" ::: "memory");                               // the loads stay here (see issue_d)
+        };
+        auto issue_l = [&](int par, const Patch &q) {
+            if constexpr (UNI) issue_u(par, q); else issue_d(par, q);
+        };
         Patch c = cur, n1 = cur, n2 = cur;
         int kc = k, k1 = 0, k2 = 0;
         bool more1 = successor(c, kc, n1, k1);
         bool more2 = more1 && successor(n1, k1, n2, k2);
-        issue_d(0, c);
-        issue_d(1, c);
+        issue_l(0, c);
+        issue_l(1, c);
         wait_vmcnt<0>();
         commit_d(0);
         commit_d(1);
         bool l1 = more1 && dma;                               // the next patch's rows are to be loaded (dbg 1: none after the first patch)
-        if (l1) { issue_d(0, n1); issue_d(1, n1); }           // the second patch's rows are in flight before the first one starts
+        if (l1) { issue_l(0, n1); issue_l(1, n1); }           // the second patch's rows are in flight before the first one starts
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         __builtin_amdgcn_s_barrier();                         // #0
         asm volatile("" ::: "memory");
@@ -492,7 +547,7 @@ __global__ __launch_bounds__(64 * (NW + LW)) void conv_stem_pt_kernel(const Stem
             if (l1) {
                 wait_vmcnt<8 * NTK>();                        // the even rows of the next patch, requested a patch ago (behind them: its odd rows, at most one pooling store)
                 commit_d(0);
-                if (l2) issue_d(0, n2);                       // even rows two patches ahead take over the registers
+                if (l2) issue_l(0, n2);                       // even rows two patches ahead take over the registers
             }
             if (!more1) break;
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
@@ -501,7 +556,7 @@ __global__ __launch_bounds__(64 * (NW + LW)) void conv_stem_pt_kernel(const Stem
             if (l1) {
                 if (l2) wait_vmcnt<8 * NTK>(); else wait_vmcnt<0>();
                 commit_d(1);                                  // odd rows of the next patch
-                if (l2) issue_d(1, n2);
+                if (l2) issue_l(1, n2);
             }
             pool_rows(c);
             c = n1; kc = k1;
@@ -891,7 +946,13 @@ static bool stem_loaders() {
     return lw;
 }
 
-// shared launcher: pool = the spatial 3x3 / 2 max-pool fused as well (y is the pooled tensor then, side its scratch)
+// A/B knob, read once: 0 = the fp32-clip form's loader waves deal their tasks per lane (variant bit 3 of tedspad_stem_pt_pool_clip_fwd by default)
+static bool stem_uniform() {
+    static const bool u = getenv("TEDSPAD_STEM_UNIFORM") == nullptr || atoi(getenv("TEDSPAD_STEM_UNIFORM")) != 0;
+    return u;
+}
+
+// shared launcher: pool =the spatial 3x3 / 2 max-pool fused as well (y is the pooled tensor then, side its scratch)
 static int32_t stem_pt_launch(const char *who, const void *x_tp, const void *w_img, const float *scale, const float *shift, void *y, void *side, int32_t n,
                               int32_t t_pairs, int32_t h, int32_t w, int32_t ho, int32_t wo, int32_t hp, int32_t wp, int32_t ldy, int32_t relu, int32_t nwg,
                               int32_t variant, int32_t dtype, bool pool, hipStream_t s, const StemPT *direct = nullptr) {
@@ -919,7 +980,10 @@ static int32_t stem_pt_launch(const char *who, const void *x_tp, const void *w_i
     int32_t rc;
 #define STEM_PT(BLOCK, LDS, ...) TS_WITH_T(dtype, rc = launch_lds<conv_stem_pt_kernel<T, __VA_ARGS__>>(who, dim3(grid), dim3(BLOCK), LDS, s, p))
     if (direct) {                                 // the 16x16x32 form reading the fp32 clip itself
-        if (stem_loaders()) STEM_PT(1024, pt_lds_pool(16), 8, true, 16, true, 8);
+        // variant bit 3: the loader waves' per-lane task deal; also where a lane's byte offset inside a plane's halo rows does not fit the buffer loads' 31 bits or a plane's offset 32
+        const bool uni = stem_uniform() && !(variant & 8) && (20L * p.sHf + 40) * 4 < (1L << 31) && (2L * p.sC + 7L * p.sT) * 4 < (1L << 32);
+        if (stem_loaders() && uni) STEM_PT(1024, pt_lds_pool(16), 8, true, 16, true, 8, true);
+        else if (stem_loaders()) STEM_PT(1024, pt_lds_pool(16), 8, true, 16, true, 8);
         else STEM_PT(512, pt_lds_pool(16), 8, true, 16, true);
     } else if (pool && (variant & 4)) {           // 16x16x32 MFMA form (8 waves; w_img in the tap-pair layout), by default with 4 loader waves issuing its halo DMA
         if (stem_loaders()) STEM_PT(768, pt_lds_pool(16), 8, true, 16, false, 4);

@@ -1154,8 +1154,11 @@ class StemPT:
         return (all(s_ % 4 == 0 and s_ >= 0 for s_ in (sn, sc, st, sh)) and (c - 1) * sc + (t + 8) * st + (h + 32) * sh + w + 64 < (1 << 31) and
                 (h + 1) // 2 >= 3 and w // 2 >= 3)
 
+    PER_LANE_LOADER = 8      # conv_pool_clip variant bit 3: the loader waves deal their tasks per lane (the form before the wave-uniform deal; TEDSPAD_STEM_UNIFORM=0 sets it for every call)
+
     def conv_pool_clip(self, x: torch.Tensor, variant=0) -> Act:
-        """conv1 + bn1 + ReLU + MaxPool3d((2,3,3), 2) (large_i3d.py:229-232) straight from the fp32 (n, c, t, h, w) clip batch: no layout pass."""
+        """conv1 + bn1 + ReLU + MaxPool3d((2,3,3), 2) (large_i3d.py:229-232) straight from the fp32 (n, c, t, h, w) clip batch: no layout pass.
+        variant: StemPT.PER_LANE_LOADER selects the loader waves' per-lane task deal (same results, A/B); bits 8..10 are the kernel's timing ablations."""
         require_cuda(x, "StemPT")
         n, c, t, h, w = x.shape
         tp = self.frame_pairs(t)
