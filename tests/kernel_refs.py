@@ -4,7 +4,8 @@ references, input conditions and case tables of the fused forward kernels (tests
 acceptance rule per tile configuration (fwd_accepts; tests/test_hip_conv_fwd_exact.py), then the inference max-pool reference, its launcher's selection restated
 (maxpool_form) and the pool / clip-layout case tables of tests/test_hip_infer_pool.py, and last the weight-image, BatchNorm-fold and gradient-unpack references (numpy) and
 case table of tests/test_hip_pack_exact.py; at the very end the MGFN kernels' references with their per-element bounds (tests/test_hip_mgfn_edges.py) and the torch
-restatements the older MGFN kernel tests share. A plain helper module: tests/test_kernel_refs.py checks every reference here against float64 torch (autograd) on
+restatements the older MGFN kernel tests share; last of all the references and case tables of the fp32 head, BCE and vote kernels
+(tests/test_hip_head_exact.py). A plain helper module: tests/test_kernel_refs.py checks every reference here against float64 torch (autograd) on
 the CPU, the -m gpu op tests (test_hip_train_kernels.py, test_hip_head_ops.py, test_hip_losses.py) compare the kernels with them.
 
 Activations are channels-last: (pixels, C) for the BatchNorm kernels, (n, t, h, w, c) for the pools, (n, h, w, c) for the resizes. Everything returned is a
@@ -2233,3 +2234,322 @@ def gemm_lengths(M):
     sequences (only the centre tap survives)."""
     ends = sorted({e for e in (1, 2, 3, 4, 31, 32, 33, 63, 64, 65, 255, 256, 257) if e < M} | {M})
     return [b - a for a, b in zip([0] + ends[:-1], ends)]
+
+
+# ---- the small fp32 kernels that close a step (tests/test_hip_head_exact.py): tedspad_linear_fwd (csrc/head.hip), tedspad_bce_head_fwd_bwd (csrc/bce_head.hip),
+# tedspad_vote_accumulate / _vote_finalize / _softmax_ce_eval (csrc/action_eval.hip) ------------------------------------------------------------------------
+# Two methods. Where the inputs can be chosen so that every partial sum is exact in fp32 in any order (integers; dyadic gradients), the kernel must EQUAL the
+# float64 reference. On realistic magnitudes every element has a bound built as above: (chain + 8) u sum |terms| for a sum, K_* u for a transcendental,
+# propagated to first order; a reference that is handed the kernel's own fp32 intermediate (the logits of the BCE head) bounds that kernel's roundings only.
+# Every reference takes `wrong=`: a kernel that is subtly wrong in one named way; test_kernel_refs.py shows that each is caught by its table.
+def _draw(seed, name, shape, n):
+    """integers 0 .. n - 1"""
+    return torch.floor(synth_tensor(seed, name, shape).to(D) * n).clamp_(0, n - 1)
+
+
+def linear_form(B, K, N):
+    """(kernel, path) of tedspad_linear_fwd, the launcher's own conditions (csrc/head.hip): K <= 32 and B >= 64: a thread per column with K <= 16 or K <= 32
+    weights in registers ('smallk16' | 'smallk32'; path 'full' where K fills them, else 'partial'); else B <= 16 and K >= 256: a wavefront per column over
+    8 or 16 rows ('cols8' | 'cols16'); else a wavefront per output ('wave'). The last three: path 'vec' (float4 loads, K % 4 == 0) or 'scalar'."""
+    if K <= 32 and B >= 64:
+        km = 16 if K <= 16 else 32
+        return "smallk%d" % km, "full" if K == km else "partial"
+    path = "vec" if K % 4 == 0 else "scalar"
+    if B <= 16 and K >= 256:
+        return ("cols8" if B <= 8 else "cols16"), path
+    return "wave", path
+
+
+LINEAR_FORMS = {("smallk16", "partial"), ("smallk16", "full"), ("smallk32", "partial"), ("smallk32", "full"), ("cols8", "vec"), ("cols8", "scalar"),
+                ("cols16", "vec"), ("cols16", "scalar"), ("wave", "vec"), ("wave", "scalar")}
+LINEAR_CASES = [      # the kernel the row is there for, B, K, N
+    ("smallk16", 64, 1, 1), ("smallk16", 65, 16, 257), ("smallk16", 97, 7, 256),                   # partial 32-row blocks; N on both sides of a 256-thread block
+    ("smallk32", 64, 17, 5), ("smallk32", 96, 32, 300), ("smallk32", 129, 24, 255),
+    ("cols8", 1, 256, 1), ("cols8", 8, 256, 5), ("cols8", 3, 260, 4), ("cols8", 8, 2050, 9),      # (3, 260, 4): one live lane in the second sweep
+    ("cols16", 9, 256, 3), ("cols16", 16, 2048, 7), ("cols16", 16, 258, 6),
+    # the near side of every dispatch boundary; (1, 12, 33): the db product of train_nets._linear_bwd
+    ("wave", 63, 16, 9), ("wave", 64, 33, 9), ("wave", 17, 256, 5), ("wave", 16, 255, 5), ("wave", 16, 252, 5), ("wave", 1, 12, 33), ("wave", 2, 4, 1),
+    ("wave", 5, 130, 33), ("wave", 24, 2048, 102),
+]
+LINEAR_EPILOGUES = [(sc, sh, relu) for sc, sh in ((0, 0), (0, 1), (1, 1), (1, 0)) for relu in (0, 1)]       # with scale, with shift, ReLU
+LINEAR_WRONG = ("drop_last_k", "row_next", "scale_next", "no_relu", "shift_first")
+
+
+def linear_chain(B, K, N):
+    """terms one output's fp32 sum chains: a float4 per 256 columns and a 6-step butterfly, a scalar per 64 columns and the butterfly, or K in one thread"""
+    form, path = linear_form(B, K, N)
+    return K if form.startswith("smallk") else chain_row(K) if path == "vec" else (K + 63) // 64 + 6
+
+
+def linear_exact_inputs(B, K, N, seed=71):
+    """x: integers in [-8, 8], w: integers in [-4, 4], scale: powers of two that differ between neighbours, shift: non-zero even integers. Column 0 of both
+    is odd; of every later column k one side is even (x for odd k, w for even k): every product but the first is even, so x . w is odd -- never 0, and neither is
+    x . w * 2^-e + an EVEN shift: no output sits on the ReLU's edge, under any of the four epilogues."""
+    tag = "lin%d_%d_%d" % (B, K, N)
+    x, w = _draw(seed, tag + "x", (B, K), 17) - 8, _draw(seed, tag + "w", (N, K), 9) - 4
+    k = torch.arange(K)
+    x[:, k % 2 == 1] = 2 * _draw(seed, tag + "xe", (B, int((k % 2 == 1).sum())), 9) - 8
+    w[:, k % 2 == 0] = 2 * _draw(seed, tag + "we", (N, int((k % 2 == 0).sum())), 5) - 4
+    x[:, 0], w[:, 0] = 2 * _draw(seed, tag + "x0", (B,), 8) - 7, 2 * _draw(seed, tag + "w0", (N,), 4) - 3
+    return x, w, pow2_scales(N), 2 * nonzero_ints(seed, tag + "b", (N,), lo=-2, hi=2)
+
+
+def linear_real_inputs(B, K, N, seed=72):
+    """the magnitudes of a head: activations of a few units, weights ~ 1 / sqrt(K), BatchNorm scales of either sign, shifts below 1"""
+    tag = "linr%d_%d_%d" % (B, K, N)
+    x, w = synth_tensor(seed, tag + "x", (B, K), -2, 2), synth_tensor(seed, tag + "w", (N, K), -1, 1) / K ** 0.5
+    scale = synth_tensor(seed, tag + "s", (N,), 0.5, 1.5) * torch.where(synth_tensor(seed, tag + "ss", (N,)) < 0.25, -1.0, 1.0)
+    return x, w, scale, synth_tensor(seed, tag + "b", (N,), -1, 1)
+
+
+def linear_ref(x, w, scale=None, shift=None, relu=False, chain=None, wrong=None):
+    """tedspad_linear_fwd: y = act(scale[n] sum_k x[b, k] w[n, k] + shift[n]). A dict: y, pre (before the ReLU), abs = sum |x||w|, and with `chain` (the terms
+    of one fp32 sum, linear_chain) bound = |scale| (chain + 8) u sum |x||w| + 2 u (|scale z| + |shift|) + FLOOR32: the sum in any order, then the product
+    and the add (one rounding where they are fused); the ReLU moves nothing further. wrong: 'drop_last_k': the sum stops one element early; 'row_next': the
+    x of row b + 1; 'scale_next': the scale of column n + 1; 'no_relu'; 'shift_first': scale (z + shift)."""
+    x, w = x.to(D), w.to(D)
+    B, K = x.shape
+    N = w.shape[0]
+    xx = x.roll(-1, 0) if wrong == "row_next" else x
+    kk = K - 1 if wrong == "drop_last_k" else K
+    z = xx[:, :kk] @ w[:, :kk].t()
+    za = x.abs() @ w.abs().t()
+    s = torch.ones(N, dtype=D) if scale is None else torch.as_tensor(scale).to(D)
+    s = s.roll(-1) if wrong == "scale_next" else s
+    b = torch.zeros(N, dtype=D) if shift is None else torch.as_tensor(shift).to(D)
+    pre = (z + b) * s if wrong == "shift_first" else z * s + b
+    out = {"y": pre.clamp_min(0.0) if (relu and wrong != "no_relu") else pre, "pre": pre, "abs": za}
+    if chain is not None:
+        out["bound"] = s.abs() * (chain + 8) * U * za + 2 * U * ((z * s).abs() + b.abs()) + FLOOR32
+    return out
+
+
+# The BCE head. (B, K, N): the smallest sizes; the largest B on one column; one workgroup whose last lane's float4 ends at K; exactly one full workgroup; both
+# limits at once (all of the 32 KB logit array; the second workgroup has one live lane); eight workgroups. B N is a power of two in all: 1 / (B N) is exact.
+BCE_CASES = [(1, 4, 1), (128, 8, 1), (1, 252, 64), (2, 256, 8), (128, 260, 64), (32, 2048, 8)]
+BCE_WRONG = ("bias_next", "div_B", "sigma_neg", "dW_row_next", "loss_scaled")
+BCE_EXACT_SCALE, BCE_DENSE_SCALE = 256.0, 3.0           # grad_scale of the two tables: a power of two (exact), and one that rounds
+
+
+def bce_exact_inputs(B, K, N, seed=5):
+    """f, W, bias, targets with every logit in {0} or |z| >= 40 (a multiple of 40): W = 40 x integers, f integers, bias 0 / +-40, targets from {0.25, 0.5, 1}.
+    Columns 0 and 1 carry the logits (both sides non-zero: z / 40 in [-3, 3]); of the others the even ones hold f only and the odd ones W only: they fill
+    dW and df without moving z. The kernel's own formulas then give sigmoid = 0.5 at 0, 1 for z >= 40 (1 + e rounds to 1) and sigmoid - y = -y for z <= -40
+    (e < half an ulp of y), so g = (sigmoid - y) / (B N) is a known dyadic number and df, dW, db are sums of dyadic products: exact in any order.
+    (The seed: one at which the single logit of (1, 4, 1) has g != 0 -- test_kernel_refs.py asserts the conditions for every row.)"""
+    tag = "bcex%d_%d_%d" % (B, K, N)
+    f, W = torch.zeros((B, K), dtype=D), torch.zeros((N, K), dtype=D)
+    f[:, :2], W[:, :2] = _draw(seed, tag + "f", (B, 2), 3) - 1, 40.0 * (_draw(seed, tag + "w", (N, 2), 3) - 1)
+    k = torch.arange(K)
+    fo, wo = (k >= 2) & (k % 2 == 0), (k >= 2) & (k % 2 == 1)
+    f[:, fo] = nonzero_ints(seed, tag + "fo", (B, int(fo.sum())), lo=-3, hi=3)
+    W[:, wo] = 40.0 * torch.where(_draw(seed, tag + "wo", (N, int(wo.sum())), 2) > 0, 1.0, -1.0) * (1 + _draw(seed, tag + "wm", (N, int(wo.sum())), 2))
+    bias = 40.0 * ((torch.arange(N) + 1) % 3 - 1).to(D)
+    y = torch.tensor([0.25, 0.5, 1.0], dtype=D)[_draw(seed, tag + "y", (B, N), 3).long()]
+    return f, W, bias, y
+
+
+def bce_dense_inputs(B, K, N, seed=75):
+    """Integer f and W that are no multiples of 40, spread over all of K (W the sparser the longer the row: logits of a few tens), integer biases up to 60 in
+    magnitude (|z| reaches 80), targets anywhere in [0, 1] with some exactly 0 and 1. The logits are integers: the kernel's forward must return them exactly."""
+    tag = "bced%d_%d_%d" % (B, K, N)
+    f = small_ints(seed, tag + "f", (B, K), lo=-3, hi=3, density=1.0)
+    W = small_ints(seed, tag + "w", (N, K), lo=-2, hi=2, density=min(1.0, 64.0 / K))
+    bias = _draw(seed, tag + "b", (N,), 121) - 60
+    if N > 1:
+        bias[0], bias[-1] = 60.0, -60.0
+    y = (synth_tensor(seed, tag + "y", (B, N)).to(D) * 1.5 - 0.25).clamp_(0.0, 1.0).to(torch.float32).to(D)
+    return f, W, bias, y
+
+
+def bce_logit_classes(z):
+    """how many logits are 0, >= 40, <= -40 -- and whether there is no other"""
+    n = [int((z == 0).sum()), int((z >= 40).sum()), int((z <= -40).sum())]
+    return n, sum(n) == z.numel()
+
+
+def bce_head_ref(f, W, bias, y, grad_scale=1.0, logits=None, wrong=None):
+    """tedspad_bce_head_fwd_bwd (the formulas at the top of csrc/bce_head.hip); W None: logits mode, f holds the logits. `logits`: the fp32 logits the kernel
+    returned, which everything after them is then derived from (the bounds cover the kernel's roundings after its K reduction only). A dict of (value,
+    bound): logits (bound None: compared exactly), loss, g, df, dW, db (the last two None in logits mode). With e = exp(-|z|), sigma = 1 / (1 + e) or
+    e / (1 + e): expf K_EXP u, the add, the division, then sigma - y (u (sigma + |y|)) and the exact or once-rounded 1 / (B N):
+      g : (K_EXP + 4) u (sigma + |y|) / (B N)
+      df: ((N + 8) u sum_n |g||W| + sum_n dg |W| + (N + 2) FLOOR32) grad_scale; dW and db likewise over B; logits mode: (dg + 2 u |g|) grad_scale
+          (dg carries FLOOR32: a g below the smallest normal may be flushed -- at z = -80, y = 0 it is e^-80 / (B N) -- and so may each of the N partial sums)
+      loss: a term max(z, 0) - z y + log1p(e) cancels, so it is held against m = |max(z, 0)| + |z y| + log1p(e): the product, the difference and the last add one
+            rounding each, log1pf K_LOG u, its argument K_EXP u (e / (1 + e) <= log1p(e)): (3 + K_EXP + K_LOG) u m; the sum chains ceil(B N / 1024) terms per
+            thread, a 6-step butterfly and the 16 wave sums, + 8 for the mean: that many u sum m, all over B N.
+    (Measured on gfx950: the device's expf is off by ~|z| u at large |z| -- DESIGN.md, "What the head, BCE and vote tests pin" -- which the g bound absorbs
+    on the dense table only just where y = 0 and z << 0: sigma - y is then e itself.)
+    wrong: 'bias_next': the bias of column n + 1; 'div_B': g over B instead of B N; 'sigma_neg': sigmoid(-z); 'dW_row_next': dW from row b + 1 of f;
+    'loss_scaled': grad_scale applied to the loss as well."""
+    f, y = f.to(D), y.to(D)
+    B, N = y.shape
+    gs = f32(grad_scale)
+    if W is None:
+        z = f.clone()
+    else:
+        W = W.to(D)
+        bb = torch.zeros(N, dtype=D) if bias is None else torch.as_tensor(bias).to(D)
+        z = f @ W.t() + (bb.roll(-1) if wrong == "bias_next" else bb)
+    if logits is not None:
+        z = logits.to(D).reshape(B, N)
+    e = torch.exp(-z.abs())
+    sig = torch.sigmoid(-z if wrong == "sigma_neg" else z)
+    g = (sig - y) / (B if wrong == "div_B" else B * N)
+    dg = (K_EXP + 4) * U * (sig + y.abs()) / (B * N) + FLOOR32
+    m = z.clamp_min(0.0) + (z * y).abs() + torch.log1p(e)
+    loss = (z.clamp_min(0.0) - z * y + torch.log1p(e)).sum() / (B * N) * (gs if wrong == "loss_scaled" else 1.0)
+    chain = (B * N + 1023) // 1024 + 6 + 16 + 8
+    out = {"logits": (z, None), "g": (g, dg), "loss": (loss.reshape(1), ((3 + K_EXP + K_LOG + chain) * U * m.sum() / (B * N) + FLOOR32).reshape(1))}
+    if W is None:
+        out.update(df=(g * gs, gs * (dg + 2 * U * g.abs()) + FLOOR32), dW=None, db=None)
+        return out
+    ga, fr = g.abs(), (f.roll(-1, 0) if wrong == "dW_row_next" else f)
+    out["df"] = (gs * (g @ W), gs * ((N + 8) * U * (ga @ W.abs()) + dg @ W.abs() + (N + 2) * FLOOR32) + FLOOR32)
+    out["dW"] = (gs * (g.t() @ fr), gs * ((B + 8) * U * (ga.t() @ f.abs()) + dg.t() @ f.abs() + (B + 2) * FLOOR32) + FLOOR32)
+    out["db"] = (gs * g.sum(0), gs * ((B + 8) * U * ga.sum(0) + dg.sum(0) + (B + 2) * FLOOR32) + FLOOR32)
+    return out
+
+
+def bce_kernel_g32(z, y):
+    """g as csrc/bce_head.hip forms it, in torch's fp32 on the CPU: e = expf(-|z|), sigma = z >= 0 ? 1 / (1 + e) : e / (1 + e), (sigma - y) * (1 / (B N))."""
+    z, y = z.to(torch.float32), y.to(torch.float32)
+    e = torch.exp(-z.abs())
+    sig = torch.where(z >= 0, 1.0 / (1.0 + e), e / (1.0 + e))
+    return (sig - y) * (torch.tensor(1.0, dtype=torch.float32) / torch.tensor(float(z.numel()), dtype=torch.float32))
+
+
+# The vote kernels: a sum per (video, class) in ROW order, one fp32 add per row -- which a host loop over float32 numpy rows reproduces bit for bit.
+VOTE_C = (2, 255, 256, 257, 1024)             # one workgroup per 256 classes: one partial, exactly one, one class into the second, four
+VOTE_B = (1, 7, 1024)
+VOTE_V = {1: 2, 7: 4, 1024: 9}                # videos per batch size; the last one is never named
+VOTE_FINAL_V = (1, 4, 5, 9)                   # four videos per workgroup of vote_finalize
+VOTE_WRONG = ("reverse", "count_reload", "first_tie")
+
+
+def vote_vids(B):
+    """Video index per row: long runs, strict alternation (every flush followed by a reload of what an earlier flush wrote), single rows. V - 1 never occurs."""
+    if B == 1:
+        return [0]
+    if B == 7:
+        return [0, 0, 1, 0, 1, 2, 0]
+    seq = [0] * 300 + [1, 2] * 100 + [3, 4, 5, 6, 7, 3, 0, 5] * 8 + [1] * 200 + [0, 3] * 80
+    seq += [(5 * i) % 8 for i in range(B - len(seq) - 40)] + [7] * 40
+    assert len(seq) == B
+    return seq
+
+
+def vote_inputs(B, C, seed=76):
+    """probability rows (softmax of logits in [-4, 4], fp32), the video of each row, and sums / counts that already hold something"""
+    tag, V = "vote%d_%d" % (B, C), VOTE_V[B]
+    probs = torch.softmax(synth_tensor(seed, tag + "z", (B, C), -4, 4), dim=1).numpy()
+    sums = synth_tensor(seed, tag + "s", (V, C), 0, 3).numpy()
+    counts = (_draw(seed, tag + "c", (V,), 4) + 1).numpy().astype(np.int32)
+    return probs, vote_vids(B), sums, counts, V
+
+
+def vote_accumulate_ref(probs, vid, sums, counts, wrong=None):
+    """tedspad_vote_accumulate, the kernel's own walk in float32 numpy: a run of rows of one video starts from what `sums` holds (also what an earlier run of
+    this launch wrote back), adds its rows one by one, is written back when the video changes; counts likewise. Returns new (sums, counts).
+    wrong = 'reverse': the rows from last to first; 'count_reload': a run of a video that was written back earlier counts one row too many."""
+    p, s, c = np.asarray(probs, np.float32), np.array(sums, np.float32, copy=True), np.array(counts, np.int32, copy=True)
+    rows = range(len(vid) - 1, -1, -1) if wrong == "reverse" else range(len(vid))
+    cur, n, acc, flushed = -1, 0, None, set()
+    for b in rows:
+        v = int(vid[b])
+        if v != cur:
+            if cur >= 0:
+                s[cur], c[cur] = acc, c[cur] + n
+                flushed.add(cur)
+            cur, n, acc = v, (1 if wrong == "count_reload" and v in flushed else 0), s[v].copy()
+        acc = acc + p[b]                      # float32 + float32: one IEEE add per class
+        n += 1
+    if cur >= 0:
+        s[cur], c[cur] = acc, c[cur] + n
+    assert s.dtype == np.float32
+    return s, c
+
+
+def vote_finalize_inputs(V, C, seed=77):
+    """sums in [0, 1), counts 1 .. 9, labels; exactly equal maxima (1.5) planted in two neighbouring lanes of video 0, and for V >= 4: in one lane (c, c + 64)
+    of video 1 where C allows, in the first and the last class of video 2; video 3 has no rows (count 0). Returns sums, counts, labels, the top-1 wanted."""
+    tag = "votef%d_%d" % (V, C)
+    sums = synth_tensor(seed, tag + "s", (V, C), 0, 1).numpy()
+    counts = (_draw(seed, tag + "c", (V,), 9) + 1).numpy().astype(np.int32)
+    c0 = min(C - 2, 130)
+    sums[0, c0] = sums[0, c0 + 1] = 1.5
+    want = [c0 + 1] + [-2] * (V - 1)
+    if V >= 4:
+        c1 = min(C - 1, 70)
+        sums[1, c1] = sums[1, max(c1 - 64, 0)] = 1.5
+        sums[2, 0] = sums[2, C - 1] = 1.5
+        counts[3] = 0
+        want[1:4] = [c1, C - 1, -1]
+    labels = np.array([(7 * v) % C for v in range(V)], np.int64)
+    labels[0] = want[0]                       # video 0 is right only under the highest-index rule
+    return sums, counts, labels, want
+
+
+def vote_finalize_ref(sums, counts, labels, wrong=None):
+    """tedspad_vote_finalize: mean = sums / float32(count) (IEEE division; a video without rows: zeros, top-1 -1, not correct), top-1 = the HIGHEST index
+    among exactly equal maxima of the mean, correct = (top-1 == label). wrong = 'first_tie': the lowest index."""
+    s, c = np.asarray(sums, np.float32), np.asarray(counts, np.int32)
+    V, C = s.shape
+    seen = c > 0
+    mean = np.where(seen[:, None], s / np.where(seen, c, 1).astype(np.float32)[:, None], np.float32(0)).astype(np.float32)
+    top = np.argmax(mean, axis=1) if wrong == "first_tie" else C - 1 - np.argmax(mean[:, ::-1], axis=1)
+    pred = np.where(seen, top, -1).astype(np.int32)
+    return mean, pred, (seen & (pred == np.asarray(labels))).astype(np.uint8)
+
+
+def sce_logits(B, C, seed=78):
+    """Rows spread over [-80, 80] as tests/test_hip_action_eval.py draws them: the maximum (80) at a different column per row, a runner-up 0.1 .. 0.5 below
+    it, one entry at -80 (C = 2: odd rows negated instead); row 0 is labelled with its top class. Returns logits (fp32), labels (int64)."""
+    z = synth_tensor(seed, "sce_z_%d_%d" % (B, C), (B, C), -80.0, 79.0)
+    lab = (synth_tensor(seed, "sce_l_%d_%d" % (B, C), (B,)) * C).long().clamp(0, C - 1)
+    for r in range(B):
+        m = (7 * r + 3) % C
+        z[r, m] = 80.0
+        z[r, (m + 2) % C if C > 2 else 1 - m] = 80.0 - 0.1 * (1 + r % 5)
+        if C > 2:
+            z[r, (m + 1) % C] = -80.0
+        elif r % 2:
+            z[r] = -z[r]
+    lab[0] = int(z[0].argmax())
+    return z, lab
+
+
+def softmax_ce_ref(z, labels):
+    """tedspad_softmax_ce_eval: softmax over the classes, -log_softmax[label] per row, its mean, the top-1 class (float64 argmax). A dict of (value, bound)
+    and pred. The kernel forms d = z - max (one rounding: u |d| in the exponent), e = expf(d) (K_EXP u), rest = the sum of e without the top class over
+    n = ceil(C / 64) + 6 chained terms, den = 1 + rest:
+      drest = sum e (u |d| + K_EXP u) + (n + 2) u rest;  dden = drest + u den
+      probs: p (u |d| + K_EXP u + dden / den + 2 u)      (the division, and slack for the second order)
+      row loss = log1p(rest) + (max - z[label]): drest / den + K_LOG u log1p(rest) + u |max - z[label]| + u |loss|
+      mean: (sum of the row bounds + (ceil(B / 64) + 6 + 2) u sum |row loss|) / B."""
+    z = z.to(D)
+    B, C = z.shape
+    mx, top = z.max(1)
+    d = z - mx[:, None]
+    e = torch.exp(d)
+    notop = torch.ones_like(e)
+    notop[torch.arange(B), top] = 0.0
+    rest = (e * notop).sum(1)
+    n = (C + 63) // 64 + 6
+    drest = (e * notop * (U * d.abs() + K_EXP * U)).sum(1) + (n + 2) * U * rest
+    den = 1.0 + rest
+    dden = drest + U * den
+    p = e / den[:, None]
+    dp = p * (U * d.abs() + K_EXP * U + (dden / den)[:, None] + 2 * U) + FLOOR32
+    gap = mx - z[torch.arange(B), labels]
+    rows = torch.log1p(rest) + gap
+    drows = drest / den + K_LOG * U * torch.log1p(rest) + U * gap.abs() + U * rows.abs() + FLOOR32
+    dmean = (drows.sum() + ((B + 63) // 64 + 8) * U * rows.abs().sum()) / B + FLOOR32
+    return {"probs": (p, dp), "row_loss": (rows, drows), "loss": (rows.mean().reshape(1), dmean.reshape(1)), "pred": top}
+
+
+def worst_ratio(got, ref, bound):
+    """the largest error / bound over the elements: what a bounded test prints per quantity"""
+    got, ref, bound = torch.as_tensor(got).to(D), torch.as_tensor(ref).to(D), torch.as_tensor(bound).to(D)
+    return float(((got.reshape(ref.shape) - ref).abs() / bound).max())

@@ -105,12 +105,111 @@ def test_tail_stage_a_keeps_its_counted_lds_waits():
         assert not moved, "fragment registers spilled / copied inside the counted-wait region: %s" % moved[:4]
 
 
+C_SCALARS = {"int32_t": ctypes.c_int32, "int64_t": ctypes.c_int64, "float": ctypes.c_float, "double": ctypes.c_double}
+HEADER_STRUCTS = {"tedspad_conv_desc": _lib.ConvDesc, "tedspad_conv_extras": _lib.ConvExtras, "tedspad_pool_desc": _lib.PoolDesc,
+                  "tedspad_pack_job": _lib.PackJob, "tedspad_fold_job": _lib.FoldJob, "tedspad_wgrad_unpack_job": _lib.WgradUnpackJob}
+
+
+def _header_code():
+    """include/tedspad_hip.h without comments and preprocessor lines"""
+    hdr = open(os.path.join(ROOT, "include", "tedspad_hip.h")).read()
+    hdr = re.sub(r"/\*.*?\*/", " ", hdr, flags=re.S)
+    hdr = re.sub(r"//[^\n]*", " ", hdr)
+    return re.sub(r"^\s*#[^\n]*", " ", hdr, flags=re.M)
+
+
+def _c_kind(decl, what):
+    """'ptr' for any pointer, else the scalar type's name: `decl` is a C type with or without a parameter name. An unknown type raises."""
+    if "*" in decl:
+        return "ptr"
+    words = [t for t in re.findall(r"[A-Za-z_][A-Za-z0-9_]*", decl) if t != "const"]
+    assert words and words[0] in C_SCALARS and len(words) <= 2, "%s: a C type this test does not know: %r" % (what, decl.strip())
+    return words[0]
+
+
+def _ctypes_kind(t):
+    """the same classes for a ctypes type of the table"""
+    if t in (ctypes.c_void_p, ctypes.c_char_p) or isinstance(t, type(ctypes.POINTER(ctypes.c_int32))):
+        return "ptr"
+    for name, ct in C_SCALARS.items():
+        if t is ct:
+            return name
+    raise AssertionError("a ctypes type this test does not know: %r" % (t,))
+
+
+def _header_prototypes():
+    """name -> (kind of the return type, [kind of each parameter]) for every function include/tedspad_hip.h declares"""
+    code = re.sub(r"\{[^{}]*\}", " ", _header_code())        # struct and enum bodies (the extern "C" braces hold no pair without a nested one)
+    protos = {}
+    for ret, name, params in re.findall(r"([A-Za-z_][A-Za-z0-9_ \t\n\*]*?)\b(tedspad_[a-z0-9_]+)\s*\(([^()]*)\)\s*;", code):
+        assert name not in protos, "%s is declared twice" % name
+        params = [p for p in params.split(",")] if params.strip() != "void" else []
+        protos[name] = (_c_kind(ret + " x", name + " (return type)"), [_c_kind(p, "%s argument %d" % (name, i)) for i, p in enumerate(params)])
+    return protos
+
+
+def test_ctypes_table_mirrors_the_header_argument_by_argument():
+    """Every prototype of include/tedspad_hip.h against _lib.SYMBOLS: the return type and every parameter, as pointer / int32_t / int64_t / float / double
+    (an int64_t stride bound as c_int32 works at test sizes and truncates at the workload's). A type the parser does not know fails. Then the field types
+    of the six structs that cross the ABI, arrays included. No GPU."""
+    protos = _header_prototypes()
+    declared = set(re.findall(r"\b(tedspad_[a-z0-9_]+)\s*\(", _header_code()))
+    assert len(protos) >= 100 and set(protos) == declared == set(_lib.SYMBOLS), set(protos) ^ declared ^ set(_lib.SYMBOLS)
+    bad = []
+    for name, (ret, args) in sorted(protos.items()):
+        res, argtypes = _lib.SYMBOLS[name]
+        if _ctypes_kind(res) != ret:
+            bad.append("%s: returns %s in the header, %s in the table" % (name, ret, _ctypes_kind(res)))
+        if len(argtypes) != len(args):
+            bad.append("%s: %d parameters in the header, %d in the table" % (name, len(args), len(argtypes)))
+            continue
+        for i, (h, t) in enumerate(zip(args, argtypes)):
+            if _ctypes_kind(t) != h:
+                bad.append("%s argument %d: %s in the header, %s in the table" % (name, i, h, _ctypes_kind(t)))
+    assert not bad, "\n".join(bad)
+    for ptr_to, struct in ((_lib.ConvDesc, "tedspad_conv_desc"), (_lib.ConvExtras, "tedspad_conv_extras"), (_lib.PoolDesc, "tedspad_pool_desc")):
+        users = [n for n, (_, a) in _lib.SYMBOLS.items() if ctypes.POINTER(ptr_to) in a]
+        assert users and all(re.search(r"\b%s\s*\([^()]*\b%s\s*\*" % (n, struct), _header_code()) for n in users), (struct, users)
+    code = _header_code()
+    for cname, cls in HEADER_STRUCTS.items():
+        body = re.search(r"typedef struct %s \{(.*?)\} %s;" % (cname, cname), code, flags=re.S).group(1)
+        fields = []
+        for decl in body.split(";"):
+            if not decl.strip():
+                continue
+            base = _c_kind(decl.split(",")[0], cname)                  # "const float *w, *scale, *out": every piece carries its own '*'
+            for piece in decl.split(","):
+                dim = re.search(r"\[(\d+)\]", piece)
+                fields.append(("ptr" if "*" in piece else base, int(dim.group(1)) if dim else 0))
+        mine = []
+        for _, t in cls._fields_:
+            n = getattr(t, "_length_", 0) if issubclass(t, ctypes.Array) else 0
+            mine.append((_ctypes_kind(t._type_ if n else t), n))
+        assert fields == mine, (cname, [i for i, (a, b) in enumerate(zip(fields, mine)) if a != b], len(fields), len(mine))
+
+
+def test_header_parser_sees_a_wrong_binding():
+    """The comparison above is not vacuous: the kinds it derives tell an int64_t from an int32_t, a float from a double, and refuse an unknown type."""
+    assert _c_kind("int64_t sn", "t") == "int64_t" != _ctypes_kind(ctypes.c_int32) and _c_kind("const float *x", "t") == "ptr" == _ctypes_kind(ctypes.POINTER(_lib.ConvDesc))
+    assert _c_kind("double eps", "t") != _ctypes_kind(ctypes.c_float) and _c_kind("const char *", "t") == _ctypes_kind(ctypes.c_char_p)
+    for unknown in ("uint8_t flag", "size_t n", "unsigned long n", "tedspad_conv_desc d"):
+        with pytest.raises(AssertionError):
+            _c_kind(unknown, "t")
+    with pytest.raises(AssertionError):
+        _ctypes_kind(ctypes.c_uint8)
+    protos = _header_prototypes()
+    assert protos["tedspad_clip_to_channels_last"][1][7:12] == ["int64_t"] * 5 and protos["tedspad_bn_fold"][1][5] == "double"
+    assert protos["tedspad_last_error"] == ("ptr", []) and protos["tedspad_stem_pt_side_bytes"] == ("int64_t", ["int32_t"] * 4)
+
+
 def test_job_structs_mirror_the_header():
     """The multi-job launches take arrays of plain C structs (include/tedspad_hip.h: tedspad_pack_job / _fold_job / _wgrad_unpack_job); the ctypes
-    mirrors must have the sizes csrc/pack.hip static_asserts and the header's field order. No GPU: a null job list is refused by the host check."""
+    mirrors must have the sizes csrc/pack.hip static_asserts and the header's field order -- and so must the descriptors every conv and pool launch takes
+    (tedspad_conv_desc / _conv_extras / _pool_desc). No GPU: a null job list is refused by the host check."""
     assert (ctypes.sizeof(_lib.PackJob), ctypes.sizeof(_lib.FoldJob), ctypes.sizeof(_lib.WgradUnpackJob)) == (120, 96, 64)
     hdr = open(os.path.join(ROOT, "include", "tedspad_hip.h")).read()
-    for cls, cname in ((_lib.PackJob, "tedspad_pack_job"), (_lib.FoldJob, "tedspad_fold_job"), (_lib.WgradUnpackJob, "tedspad_wgrad_unpack_job")):
+    for cls, cname in ((_lib.PackJob, "tedspad_pack_job"), (_lib.FoldJob, "tedspad_fold_job"), (_lib.WgradUnpackJob, "tedspad_wgrad_unpack_job"),
+                       (_lib.ConvDesc, "tedspad_conv_desc"), (_lib.ConvExtras, "tedspad_conv_extras"), (_lib.PoolDesc, "tedspad_pool_desc")):
         body = re.search(r"typedef struct %s \{(.*?)\} %s;" % (cname, cname), hdr, flags=re.S).group(1)
         body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
         names = []

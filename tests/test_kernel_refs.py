@@ -1,6 +1,9 @@
 """CPU: the float64 references of tests/kernel_refs.py against float64 torch (autograd) at the shapes the -m gpu op tests use, to 1e-12 relative, and the
 properties of the two value generators those tests rely on (ties in the max-pool windows, exactness of dyadic sums). Last, the MGFN references: equal to float64
-torch, torch's fp32 evaluation inside every per-element bound, a list of wrong references outside."""
+torch, torch's fp32 evaluation inside every per-element bound, a list of wrong references outside. Then the same for the fp32 head, BCE and vote kernels
+(tests/test_hip_head_exact.py): the case tables reach every kernel form, their inputs meet the conditions of exactness, every `wrong=` mutant is caught."""
+import itertools
+
 import numpy as np
 import pytest
 import torch
@@ -1083,3 +1086,278 @@ def test_mgfn_transpose_and_wgrad_refs(M):
     inside(at.float() @ dyt.float().t(), rb, "wgrad")
     not_vacuous(rb, "wgrad")
     assert R.mgfn_wgrad_slices(ldk, taps * C, N)[1] == (1 if M <= 128 else 2 if M == 129 else 3)
+
+
+# ---- the fp32 head, BCE and vote kernels: the conditions of tests/test_hip_head_exact.py and its sensitivity, on the references alone --------------------------
+def _lin_ep(scale, shift, sc, sh):
+    return (scale if sc else None), (shift if sh else None)
+
+
+def test_linear_table_reaches_every_form():
+    """Every row reaches the kernel it names, and the table reaches every kernel on both of its paths (a later change of the launcher's thresholds cannot
+    silently empty one); the boundaries the dispatch turns on are all present, from both sides."""
+    seen = set()
+    for form, B, K, N in R.LINEAR_CASES:
+        got = R.linear_form(B, K, N)
+        assert got[0] == form, (form, B, K, N, got)
+        seen.add(got)
+    assert seen == R.LINEAR_FORMS, seen ^ R.LINEAR_FORMS
+    shapes = {c[1:] for c in R.LINEAR_CASES}
+    assert len(shapes) == len(R.LINEAR_CASES)
+    assert {B for B, _, _ in shapes} >= {1, 8, 9, 16, 17, 63, 64, 65} and {K for _, K, _ in shapes} >= {16, 17, 32, 33, 255, 256}
+    assert any(B >= 64 and B % 32 for B, K, N in shapes if K <= 32) and {N for B, K, N in shapes if K <= 32 and B >= 64} >= {255, 256, 257}
+    assert R.linear_form(63, 16, 9)[0] == R.linear_form(64, 33, 9)[0] == R.linear_form(17, 256, 5)[0] == R.linear_form(16, 255, 5)[0] == "wave"
+    assert R.linear_chain(8, 2048, 3) == 38 and R.linear_chain(8, 2050, 3) == 39 and R.linear_chain(64, 24, 3) == 24
+
+
+@pytest.mark.parametrize("form,B,K,N", R.LINEAR_CASES)
+def test_linear_exact_inputs_meet_the_conditions(form, B, K, N):
+    """Ranges; sum |x||w| an integer below 2^24 (so is every partial sum, in any order; the epilogue's grid of 2^-2 keeps it exact); telling scales and
+    shifts; no pre-activation exactly 0 under any epilogue; the reference equals float64 torch. The ReLU's share of zeros: per row with 16 outputs or more
+    between 20 % and 80 % (fewer outputs cannot hold a share: they count in the table's total, below)."""
+    x, w, scale, shift = R.linear_exact_inputs(B, K, N)
+    assert float(x.abs().max()) <= 8 and float(w.abs().max()) <= 4 and bool((x == x.round()).all()) and bool((w == w.round()).all())
+    assert R.bn_is_telling(scale, shift) and (N == 1 or float(scale.min()) < float(scale.max()))
+    for sc, sh, relu in R.LINEAR_EPILOGUES:
+        s, b = _lin_ep(scale, shift, sc, sh)
+        r = R.linear_ref(x, w, s, b, relu)
+        assert R.exact_in_fp32(r["abs"]) and R.exact_in_fp32(r["abs"] + 3.0)
+        assert torch.equal(r["y"].float().to(D), r["y"]) and bool((r["pre"] * 4 == (r["pre"] * 4).round()).all())
+        assert bool((r["pre"] != 0).all())
+        want = F.linear(x, w * (s[:, None] if sc else 1.0), b)
+        assert torch.equal(r["y"], F.relu(want) if relu else want)
+        if relu and B * N >= 16:
+            zero = float((r["y"] == 0).double().mean())
+            assert 0.2 <= zero <= 0.8, (sc, sh, zero)
+
+
+def test_linear_relu_share_over_the_table_and_mutants_are_caught():
+    """Over the whole table the ReLU zeroes 20 .. 80 % of the outputs under every epilogue; every wrong kernel of LINEAR_WRONG is unequal to the exact reference
+    on at least one row (and the rows that catch it are printed)."""
+    zero, total = {}, {}
+    caught = {m: [] for m in R.LINEAR_WRONG}
+    for form, B, K, N in R.LINEAR_CASES:
+        x, w, scale, shift = R.linear_exact_inputs(B, K, N)
+        for sc, sh, relu in R.LINEAR_EPILOGUES:
+            s, b = _lin_ep(scale, shift, sc, sh)
+            y = R.linear_ref(x, w, s, b, relu)["y"]
+            if relu:
+                zero[sc, sh] = zero.get((sc, sh), 0) + int((y == 0).sum())
+                total[sc, sh] = total.get((sc, sh), 0) + y.numel()
+            for m in R.LINEAR_WRONG:
+                if not torch.equal(R.linear_ref(x, w, s, b, relu, wrong=m)["y"], y):
+                    caught[m].append((B, K, N, sc, sh, relu))
+    for k in zero:
+        assert 0.2 <= zero[k] / total[k] <= 0.8, (k, zero[k] / total[k])
+    for m, rows in caught.items():
+        print(m, len(rows))
+        assert rows, "%s equals the reference on every row" % m
+        assert len({r[:3] for r in rows}) >= 10, (m, "caught on few shapes only")
+
+
+@pytest.mark.parametrize("form,B,K,N", R.LINEAR_CASES)
+def test_linear_real_bound_holds_torch_fp32_and_rejects_the_mutants(form, B, K, N):
+    x, w, scale, shift = R.linear_real_inputs(B, K, N)
+    assert x.dtype == w.dtype == scale.dtype == shift.dtype == F32T
+    chain = R.linear_chain(B, K, N)
+    for sc, sh, relu in ((1, 1, 1), (0, 1, 0)):
+        s, b = _lin_ep(scale, shift, sc, sh)
+        r = R.linear_ref(x, w, s, b, relu, chain=chain)
+        want = F.linear(x.to(D), w.to(D)) * (s.to(D) if sc else 1.0) + b.to(D)
+        assert close(r["y"], F.relu(want) if relu else want)
+        v32 = F.linear(x, w) * (s if sc else 1.0) + b
+        inside(F.relu(v32) if relu else v32, (r["y"], r["bound"]), "linear")
+        not_vacuous((r["y"], r["bound"]), "linear", 1e-4)
+        for m in R.LINEAR_WRONG:
+            moved = not torch.equal(R.linear_ref(x, w, s, b, relu, wrong=m)["y"], r["y"])
+            if moved:
+                outside(R.linear_ref(x, w, s, b, relu, wrong=m)["y"], (r["y"], r["bound"]), m)
+
+
+def _bce_autograd(f, W, bias, y, gs):
+    f, W, bias = (t.to(D).clone().requires_grad_() for t in (f, W, bias))
+    z = f @ W.t() + bias
+    loss = F.binary_cross_entropy_with_logits(z, y.to(D))
+    (loss * gs).backward()
+    return z.detach(), loss.detach(), f.grad, W.grad, bias.grad
+
+
+def _representable(t):
+    return torch.equal(t.float().to(D), t)
+
+
+@pytest.mark.parametrize("B,K,N", R.BCE_CASES)
+def test_bce_exact_inputs_meet_the_conditions(B, K, N):
+    """The logits are 0 or at least 40 in magnitude, all three classes present where there are 16 logits; the kernel's formulas in torch's fp32 give g exactly
+    (the float64 g is its own fp32 rounding to 2^-50); df, dW, db are fp32 numbers; at least 30 % of df and of dW are non-zero; the reference equals float64
+    autograd where sigmoid is not saturated beyond float64 (everywhere: 1e-12)."""
+    assert (B * N) & (B * N - 1) == 0 and K % 4 == 0 and B <= 128 and N <= 64
+    f, W, bias, y = R.bce_exact_inputs(B, K, N)
+    assert bool((W % 40 == 0).all()) and bool((f == f.round()).all()) and set(bias.tolist()) <= {0.0, 40.0, -40.0} and set(y.flatten().tolist()) <= {0.25, 0.5, 1.0}
+    r = R.bce_head_ref(f, W, bias, y, R.BCE_EXACT_SCALE)
+    z = r["logits"][0]
+    n, only = R.bce_logit_classes(z)
+    assert only and (B * N < 16 or min(n) >= 1), n
+    assert R.exact_in_fp32(f.abs() @ W.abs().t() + bias.abs())
+    g = r["g"][0]
+    g32 = R.bce_kernel_g32(z, y).to(D)
+    assert float((g - g32).abs().max()) <= 2.0 ** -50 and float((g - g.float().to(D)).abs().max()) <= 2.0 ** -50
+    gd = g32                                                               # the dyadic g: sums of its products are exact in float64 too
+    df, dW, db = R.BCE_EXACT_SCALE * (gd @ W), R.BCE_EXACT_SCALE * (gd.t() @ f), R.BCE_EXACT_SCALE * gd.sum(0)
+    for name, v in (("df", df), ("dW", dW), ("db", db)):
+        assert _representable(v), name
+        assert torch.equal(r[name][0].float().to(D), v), name               # what the GPU test compares with: the reference, rounded to fp32, IS the dyadic value
+        unit = 2.0 ** -2 / (B * N)                                          # every term is a multiple of this; the sum of the magnitudes in units of it stays below 2^24
+    assert R.exact_in_fp32((gd.abs() @ W.abs()) / unit) and R.exact_in_fp32((gd.abs().t() @ f.abs()) / unit) and R.exact_in_fp32(gd.abs().sum(0) / unit)
+    assert float((df != 0).double().mean()) >= 0.3 and float((dW != 0).double().mean()) >= 0.3, (float((df != 0).double().mean()), float((dW != 0).double().mean()))
+    assert bool((g32 != 0).any())
+    za, la, dfa, dWa, dba = _bce_autograd(f, W, bias, y, R.BCE_EXACT_SCALE)
+    assert torch.equal(za, z) and close(r["loss"][0], la.reshape(1)) and close(r["df"][0], dfa, 1e-10) and close(r["dW"][0], dWa, 1e-10) and close(r["db"][0], dba, 1e-10)
+
+
+@pytest.mark.parametrize("B,K,N", R.BCE_CASES)
+def test_bce_dense_bounds_hold_torch_fp32(B, K, N):
+    """The dense table: integer logits that are exact in fp32, |z| from 0 to beyond 80 over the table, targets inside (0, 1); the reference equals float64
+    autograd, torch's fp32 evaluation of the same formulas lies inside every bound, no bound is vacuous."""
+    f, W, bias, y = R.bce_dense_inputs(B, K, N)
+    assert R.exact_in_fp32(f.abs() @ W.abs().t() + bias.abs()) and _representable(y)
+    assert bool((f[f != 0] % 40 != 0).all()) and bool((W[W != 0] % 40 != 0).all()) and float((f != 0).double().mean()) > 0.5
+    for k0 in range(0, K, 256):                                             # every workgroup's slice of columns holds weights: no df / dW slice is all zeros
+        assert bool((W[:, k0:k0 + 256] != 0).any()) and bool((f[:, k0:k0 + 256] != 0).any())
+    gs = R.BCE_DENSE_SCALE
+    r = R.bce_head_ref(f, W, bias, y, gs)
+    z = r["logits"][0]
+    za, la, dfa, dWa, dba = _bce_autograd(f, W, bias, y, gs)
+    assert torch.equal(za, z) and close(r["loss"][0], la.reshape(1)) and close(r["df"][0], dfa, 1e-10) and close(r["dW"][0], dWa, 1e-10) and close(r["db"][0], dba, 1e-10)
+    f32_, W32, b32, y32 = (t.float().requires_grad_(i < 3) for i, t in enumerate((f, W, bias, y)))
+    z32 = f32_ @ W32.t() + b32
+    l32 = F.binary_cross_entropy_with_logits(z32, y32)
+    (l32 * gs).backward()
+    r2 = R.bce_head_ref(f, W, bias, y, gs, logits=z32.detach())
+    inside(l32.detach().reshape(1), r2["loss"], "loss")
+    inside(f32_.grad, r2["df"], "df")
+    inside(W32.grad, r2["dW"], "dW")
+    inside(b32.grad, r2["db"], "db")
+    inside(R.bce_kernel_g32(z, y), r2["g"], "g")
+    for k, rel in (("loss", 1e-4), ("df", 1e-4), ("dW", 1e-4), ("db", 1e-4)):
+        not_vacuous(r2[k], k, rel)
+
+
+def test_bce_tables_cover_the_logit_range_and_catch_every_mutant():
+    zs, ys = [], []
+    caught = {m: set() for m in R.BCE_WRONG}
+    for B, K, N in R.BCE_CASES:
+        fx, Wx, bx, yx = R.bce_exact_inputs(B, K, N)
+        ex = R.bce_head_ref(fx, Wx, bx, yx, R.BCE_EXACT_SCALE)
+        fd, Wd, bd, yd = R.bce_dense_inputs(B, K, N)
+        de = R.bce_head_ref(fd, Wd, bd, yd, R.BCE_DENSE_SCALE)
+        zs.append(de["logits"][0].flatten())
+        ys.append(yd.flatten())
+        for m in R.BCE_WRONG:
+            wx = R.bce_head_ref(fx, Wx, bx, yx, R.BCE_EXACT_SCALE, wrong=m)
+            if any(not torch.equal(wx[k][0], ex[k][0]) for k in ("logits", "df", "dW", "db")):
+                caught[m].add(("exact", B, K, N))
+            # the dense test hands the reference the kernel's logits: a wrong kernel's own
+            wd = R.bce_head_ref(fd, Wd, bd, yd, R.BCE_DENSE_SCALE, wrong=m)
+            rd = R.bce_head_ref(fd, Wd, bd, yd, R.BCE_DENSE_SCALE, logits=wd["logits"][0])
+            if not torch.equal(wd["logits"][0], de["logits"][0]) or any(R.worst(wd[k][0], *rd[k]) for k in ("loss", "df", "dW", "db")):
+                caught[m].add(("dense", B, K, N))
+    z, y = torch.cat(zs), torch.cat(ys)
+    assert float(z.abs().max()) >= 80 and float((z.abs() < 5).double().mean()) > 0.02 and bool(((y > 0) & (y < 1)).any()) and bool((y == 0).any()) and bool((y == 1).any())
+    for m, rows in caught.items():
+        print(m, sorted(rows))
+        assert rows, "%s is caught on no row" % m
+    assert any(r[0] == "dense" for r in caught["loss_scaled"])              # only the loss moves: the exact table does not compare it exactly
+
+
+@pytest.mark.parametrize("N", [1, 64])
+def test_bce_logits_mode_reference(N):
+    """logits mode at (128, 64) and (1, 1): f holds logits from {0, +-40 m}; g is exact as in the exact table and df = g * grad_scale."""
+    B = 128 if N == 64 else 1
+    z = 40.0 * (R._draw(79, "bcel%d" % N, (B, N), 5) - 2)
+    y = torch.tensor([0.25, 0.5, 1.0], dtype=D)[R._draw(79, "bcely%d" % N, (B, N), 3).long()]
+    r = R.bce_head_ref(z, None, None, y, R.BCE_EXACT_SCALE)
+    g32 = R.bce_kernel_g32(z, y).to(D)
+    assert float((r["g"][0] - g32).abs().max()) <= 2.0 ** -50 and _representable(g32 * R.BCE_EXACT_SCALE) and r["dW"] is None
+    assert torch.equal(r["df"][0].float().to(D), g32 * R.BCE_EXACT_SCALE)
+    assert N == 1 or min(R.bce_logit_classes(z)[0]) >= 1
+    zz = z.clone().requires_grad_()
+    F.binary_cross_entropy_with_logits(zz, y).backward()
+    assert close(r["df"][0], zz.grad * R.BCE_EXACT_SCALE, 1e-10)
+
+
+@pytest.mark.parametrize("B", R.VOTE_B)
+@pytest.mark.parametrize("C", R.VOTE_C)
+def test_vote_accumulate_ref_and_its_sensitivity(B, C):
+    """The host walk against float64 (at most B + 1 roundings per sum), two launches over a split batch equal to one, the last video untouched; and the order matters: the rows in reverse change at least one bit (B > 1: one row has one order), a miscounted reloaded run changes
+    the counts (B > 1)."""
+    probs, vid, sums, counts, V = R.vote_inputs(B, C)
+    assert probs.dtype == sums.dtype == np.float32 and bool((sums != 0).all()) and bool((counts > 0).all()) and max(vid) == V - 2 and min(vid) == 0
+    s, c = R.vote_accumulate_ref(probs, vid, sums, counts)
+    want = sums.astype(np.float64)
+    for b, v in enumerate(vid):
+        want[v] += probs[b].astype(np.float64)
+    assert np.abs(s - want).max() <= (B + 1) * 2.0 ** -24 * want.max()
+    assert c.tolist() == [int(counts[v]) + vid.count(v) for v in range(V)]
+    assert np.array_equal(s[V - 1], sums[V - 1]) and c[V - 1] == counts[V - 1]
+    if B > 1:
+        h = B // 2 + 1
+        s2, c2 = R.vote_accumulate_ref(probs[h:], vid[h:], *R.vote_accumulate_ref(probs[:h], vid[:h], sums, counts))
+        assert np.array_equal(s2.view(np.int32), s.view(np.int32)) and np.array_equal(c2, c)
+        runs = [v for i, v in enumerate(vid) if i == 0 or vid[i - 1] != v]
+        assert len(runs) > len(set(runs)), "no video is reloaded after a flush"
+        sr, cr = R.vote_accumulate_ref(probs, vid, sums, counts, wrong="reverse")
+        assert np.array_equal(cr, c) and not np.array_equal(sr.view(np.int32), s.view(np.int32)), "the reverse order changes no bit"
+        sc_, cc = R.vote_accumulate_ref(probs, vid, sums, counts, wrong="count_reload")
+        assert np.array_equal(sc_, s) and not np.array_equal(cc, c)
+    if B == 1024:
+        alt = sum(1 for i in range(2, B) if vid[i] == vid[i - 2] != vid[i - 1])
+        assert alt >= 300 and max(len(list(g)) for _, g in itertools.groupby(vid)) >= 200
+
+
+@pytest.mark.parametrize("V", R.VOTE_FINAL_V)
+@pytest.mark.parametrize("C", R.VOTE_C)
+def test_vote_finalize_ref_and_the_tie_rule(V, C):
+    sums, counts, labels, want = R.vote_finalize_inputs(V, C)
+    mean, pred, correct = R.vote_finalize_ref(sums, counts, labels)
+    assert mean.dtype == np.float32 and pred.dtype == np.int32 and correct.dtype == np.uint8
+    for v in range(V):
+        if counts[v] > 0:
+            assert np.abs(mean[v] - sums[v].astype(np.float64) / counts[v]).max() <= 2.0 ** -24 * 1.5
+            assert pred[v] == np.flip(np.argsort(mean[v], kind="stable"))[0] and correct[v] == (pred[v] == labels[v])
+        else:
+            assert not mean[v].any() and pred[v] == -1 and correct[v] == 0
+    assert [int(p) for p, w in zip(pred, want) if w != -2] == [w for w in want if w != -2]
+    assert correct[0] == 1 and (V == 1 or (0 in correct.tolist() and int(counts[3]) == 0))
+    _, p1, c1 = R.vote_finalize_ref(sums, counts, labels, wrong="first_tie")
+    assert not np.array_equal(p1, pred) and not np.array_equal(c1, correct)
+    if C == 1024 and V >= 4:
+        assert sums[2, 0] == sums[2, 1023] == sums[2].max() and pred[2] == 1023
+    if C > 70 and V >= 4:
+        assert sums[1, 6] == sums[1, 70] == sums[1].max() and pred[1] == 70           # the same lane, 64 apart
+    assert sums[0, pred[0]] == sums[0, pred[0] - 1] == sums[0].max()                    # two neighbouring lanes
+
+
+@pytest.mark.parametrize("C", [2, 65])
+def test_softmax_ce_ref_at_the_batch_limit(C):
+    """B = 1024: the reference equals float64 torch, torch's fp32 softmax / cross entropy lies inside every bound, the bounds are not vacuous, the float64
+    top-1 is no rounding matter, and a row loss taken at the wrong label or a mean over B - 1 rows is outside."""
+    B = 1024
+    z, lab = R.sce_logits(B, C)
+    assert z.dtype == F32T and float(z.abs().max()) == 80.0
+    r = R.softmax_ce_ref(z, lab)
+    z64 = z.to(D)
+    top2 = torch.topk(z64, 2, dim=1).values
+    assert float((top2[:, 0] - top2[:, 1]).min()) >= 0.05 and torch.equal(r["pred"], z64.argmax(1))
+    rows64 = F.cross_entropy(z64, lab, reduction="none")
+    assert close(r["probs"][0], torch.softmax(z64, 1)) and close(r["row_loss"][0], rows64, 1e-9) and close(r["loss"][0], rows64.mean().reshape(1), 1e-9)
+    rows32 = F.cross_entropy(z, lab, reduction="none")
+    inside(torch.softmax(z, 1), r["probs"], "probs")
+    inside(rows32, r["row_loss"], "row loss")
+    inside(rows32.mean().reshape(1), r["loss"], "loss")
+    not_vacuous(r["probs"], "probs", 1e-4)
+    not_vacuous(r["row_loss"], "row loss", 1e-4)
+    not_vacuous(r["loss"], "loss", 1e-4)
+    outside(F.cross_entropy(z64, (lab + 1) % C, reduction="none"), r["row_loss"], "the loss of the next label")
+    outside((rows64.sum() / (B - 1)).reshape(1), r["loss"], "a mean over B - 1 rows")
+    outside(torch.softmax(z64 * (1 + 2.0 ** -17), 1), r["probs"], "logits off by 2^-17 relative")
