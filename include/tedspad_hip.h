@@ -560,6 +560,18 @@ int32_t tedspad_frames_crop_resize_tp(const void *frames, int32_t in_is_float, i
                                       int32_t cw, int32_t oh, int32_t ow, const int32_t *ytab, const int32_t *xtab, float divisor, int32_t flip,
                                       void *records, int32_t pad_t, int32_t stride_t, int32_t t_pairs, int32_t dtype, void *stream);
 
+/* torchvision's ten_crop of size (ch, cw) in place of the single crop box: the records X[10 * n_clips][tp][oh][b][ow/2][24] of all ten crops of every clip,
+ * clip time i / crop k at index 10 * i + k, k in torchvision's order (tl, tr, bl, br, centre, then the same five of the horizontally flipped frame). Replaces the
+ * ten tedspad_frames_crop_resize_tp calls over the boxes (0,0) (0,W-cw) (H-ch,0) (H-ch,W-cw) (yc,xc) without flip and (0,W-cw) (0,0) (H-ch,W-cw) (H-ch,0)
+ * (yc,W-cw-xc) with flip, each writing every tenth clip, bit for bit: per output row the vertical pass runs once per row origin (three, not ten), the horizontal
+ * pass once per distinct box, and a flipped crop is the store of its box's values right to left. (yc, xc): the centre crop's origin, torchvision's center_crop
+ * rule (half to even). The other arguments as tedspad_frames_crop_resize_tp; (3 * n_clips * oh + 8) * (t_pairs + 1) < 2^31; LDS: 48 * ow + 16 * W * C + 1024
+ * bytes of the CU's 160 KB (four full-width row buffers: 101.5 KB for a 1080 x 1920 source at 224 columns). */
+int32_t tedspad_frames_ten_crop_tp(const void *frames, int32_t in_is_float, int32_t T, int32_t H, int32_t W, int32_t C, int32_t n_clips,
+                                   int32_t first, int32_t clip_step, int32_t frame_step, int32_t t_clip, int32_t ch, int32_t cw, int32_t yc,
+                                   int32_t xc, int32_t oh, int32_t ow, const int32_t *ytab, const int32_t *xtab, float divisor, void *records,
+                                   int32_t pad_t, int32_t stride_t, int32_t t_pairs, int32_t dtype, void *stream);
+
 /* `shanghai_frames_dataset.augmentation` (feature_extraction/shanghai_dl.py:27-40): uint8 frames (T,H,W,C) -> crop box -> Pillow's
  * two-pass BILINEAR resize with its 8-bit intermediate image (what torchvision's resize does for a PIL image) -> to_tensor (/255)
  * -> fp32 out[t*so_t + c*so_c + y*so_h + x*so_w]. ytab / xtab: device tables of (2 + taps) int32 per output index

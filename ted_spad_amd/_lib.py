@@ -122,6 +122,7 @@ SYMBOLS = {
     "tedspad_resize_aa_table": (_I32, [_I32, _I32, _P]),
     "tedspad_frames_crop_resize": (_I32, [_P] + [_I32] * 11 + [_P, _P, C.c_float, _I32, _P] + [_I64] * 4 + [_P]),
     "tedspad_frames_crop_resize_tp": (_I32, [_P] + [_I32] * 16 + [_P, _P, C.c_float, _I32, _P] + [_I32] * 4 + [_P]),
+    "tedspad_frames_ten_crop_tp": (_I32, [_P] + [_I32] * 16 + [_P, _P, C.c_float, _P] + [_I32] * 4 + [_P]),
     "tedspad_frames_crop_resize_pil": (_I32, [_P] + [_I32] * 10 + [_P, _I32, _P, _I32, _P] + [_I64] * 4 + [_P]),
     "tedspad_frames_crop_resize_act": (_I32, [_P] + [_I32] * 16 + [_P, _P, C.c_float, _I32, _P] + [_I32] * 2 + [_P]),
     "tedspad_frames_crop_resize_pil_act": (_I32, [_P] + [_I32] * 15 + [_P, _I32, _P, _I32, _P] + [_I32] * 2 + [_P]),

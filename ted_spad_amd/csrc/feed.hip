@@ -266,6 +266,174 @@ __global__ __launch_bounds__(256) void crop_resize_tp_kernel(const ResizeTpKP q)
     }
 }
 
+// torchvision's ten_crop in front of the same resize (preprocess.ten_crop_boxes: tl, tr, bl, br, centre of the frame, then the same five of the horizontally
+// flipped frame), all ten crops' records X[10*n + crop] in one launch. The ten boxes have three row origins (0, yc, H - ch), and a crop of the flipped frame is
+// the mirror image of a crop of the unflipped one: crop 5 (flipped tl) = crop 1 (tr) written right to left, 6 = mirror of 0, 7 = of 3, 8 = of 2, and crop 9 is the
+// mirror of the box at column W - cw - xc -- which is crop 4's box only when W - cw is even (center_crop rounds half to even: xc = 14 of 27 puts the flipped
+// frame's centre crop at column 13).
+// A workgroup owns one output row of one quad of frames (as crop_resize_tp_kernel) of one ROW ORIGIN: the vertical pass runs once over the columns its boxes
+// cover (the full width for the corner origins), the horizontal pass once per distinct column origin (two for the corners; one for the centre, two when W - cw is
+// odd) into one LDS tile of half records each, and every tile leaves up to twice per record half: in record order, and for a flipped crop in reversed record
+// order (pixel ox of the mirror = pixel ow - 1 - ox: the other plane, pair ow/2 - 1 - wq). Same helpers and source expressions as crop_resize_tp_kernel: every
+// record has the bits of the ten launches it replaces.
+// Block order: the quads of one (row, row origin) write the two halves of the same records, and the hardware deals consecutive blocks round-robin over the 8
+// XCDs, each with an L2 of its own, so in hardware order the two halves of a cache line leave two L2s as two partial writes. The kernel numbers its work so that
+// the tp_n + 1 quads of a row are blocks b, b + 8, ... : one XCD (as observed; a placement the result does not depend on), whose L2 joins the halves. That alone
+// took the launch from 3.10 ms to 1.37 ms at 370 clips of 224 x 224; the column table read from global memory instead of a copy in LDS
+// (27 KB, six workgroups per CU, instead of 33 KB, four) gave 1.24 ms.
+struct TenCropKP {
+    ResizeTpKP q;               // q.r.y0, q.r.x0 and q.r.flip are not used
+    int yc, xc;                 // the centre crop's origin (preprocess.center_crop_box)
+    int nblk;                   // (clip time, output row, row origin, quad) items; the grid is rounded up to a multiple of 8 * (tp_n + 1)
+};
+
+template <typename In, typename T>
+__global__ __launch_bounds__(256) void ten_crop_tp_kernel(const TenCropKP kp) {
+    constexpr int FG = 4;
+    extern __shared__ __attribute__((aligned(16))) unsigned char lds_tc[];
+    const ResizeTpKP &q = kp.q;
+    const ResizeKP &p = q.r;
+    const int wq_n = p.ow >> 1;
+    const int tile8 = 2 * wq_n * 3;
+    uint2 *tile = reinterpret_cast<uint2 *>(lds_tc);                 // [column origin a, b][plane][wq][3 x 8 B]
+    const int rbuf = p.W * p.C;                                      // a frame's row buffer: the full width
+    float *rows = reinterpret_cast<float *>(lds_tc + (size_t)2 * tile8 * 8);    // [FG][rbuf]
+    float *lut = rows + FG * rbuf;                                   // [256] (uint8 input, divisor != 255)
+    const int32_t *xt = p.xtab;
+    const int nq = q.tp_n + 1;
+    const int slot = blockIdx.x >> 3;                                // blocks b, b + 8, ... in turn: the quads of one row, then the next row of this residue
+    const int bid = ((slot / nq) * 8 + (blockIdx.x & 7)) * nq + slot % nq;
+    if (bid >= kp.nblk) return;                                      // the grid's rounding (uniform)
+    const int qd = bid % nq;
+    const int grp = (bid / nq) % 3, rowid = bid / (3 * nq);          // row origin: 0 top, 1 centre, 2 bottom
+    const int n = rowid / p.oh, oy = rowid % p.oh;
+    const int f0 = 4 * qd - q.pt;
+    const bool div255 = p.div == 255.0f;
+    const int y0 = grp == 0 ? 0 : grp == 1 ? kp.yc : p.H - p.ch;
+    const int xa = grp == 1 ? kp.xc : 0, xb = p.W - p.cw - xa;       // column origins: of the direct crop, and of the box whose mirror is the flipped frame's crop
+    const int x_lo = xa < xb ? xa : xb;
+    const int ncol = xa == xb ? 1 : 2;
+    const int span = ((xa < xb ? xb : xa) + p.cw - x_lo) * p.C;      // <= rbuf
+    for (int i = threadIdx.x; i < ncol * tile8; i += 256) tile[i] = make_uint2(0u, 0u);
+    if (sizeof(In) == 1 && !div255) lut[threadIdx.x] = (float)threadIdx.x / p.div;
+    const int32_t *ye = p.ytab + (size_t)oy * (2 + p.ytaps);
+    const int yn = ye[1];
+    const float *wy = (const float *)(ye + 2);
+    const long rstride = (long)p.W * p.C;
+    const In *base[FG];
+    bool live[FG];
+#pragma unroll
+    for (int ff = 0; ff < FG; ++ff) {
+        const long fr = (long)q.first + (long)n * q.clip_step + (long)(f0 + ff) * q.frame_step;
+        live[ff] = f0 + ff >= 0 && f0 + ff < q.t_clip && fr >= 0 && fr < p.T;
+        base[ff] = (const In *)p.in + (((live[ff] ? fr : 0) * p.H + y0 + ye[0]) * p.W + x_lo) * p.C;
+    }
+    if constexpr (sizeof(In) == 1) {
+        if (!div255) __syncthreads();
+        for (int g = threadIdx.x; 4 * g < span; g += 256) {
+            float acc[FG][4];
+#pragma unroll
+            for (int ff = 0; ff < FG; ++ff)
+#pragma unroll
+                for (int k = 0; k < 4; ++k) acc[ff][k] = 0.f;
+            for (int j = 0; j < yn; j++) {
+                unsigned w4[FG];
+#pragma unroll
+                for (int ff = 0; ff < FG; ++ff) w4[ff] = live[ff] ? load_u8x4(reinterpret_cast<const uint8_t *>(base[ff]) + j * rstride + 4 * g, q.in_end) : 0u;
+#pragma unroll
+                for (int ff = 0; ff < FG; ++ff)
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) {
+                        acc[ff][k] += wy[j] * u8_px((w4[ff] >> (8 * k)) & 255u, div255, lut);
+                    }
+            }
+#pragma unroll
+            for (int ff = 0; ff < FG; ++ff)
+#pragma unroll
+                for (int k = 0; k < 4; ++k)
+                    if (4 * g + k < span) rows[ff * rbuf + 4 * g + k] = acc[ff][k];
+        }
+    } else {
+        for (int e = threadIdx.x; e < span; e += 256) {
+            float acc[FG];
+#pragma unroll
+            for (int ff = 0; ff < FG; ++ff) acc[ff] = 0.f;
+            for (int j = 0; j < yn; j++) {
+#pragma unroll
+                for (int ff = 0; ff < FG; ++ff) acc[ff] += wy[j] * (live[ff] ? load_px<In>(base[ff] + j * rstride + e, p.div) : 0.f);
+            }
+#pragma unroll
+            for (int ff = 0; ff < FG; ++ff) rows[ff * rbuf + e] = acc[ff];
+        }
+    }
+    __syncthreads();
+    for (int it = threadIdx.x; it < ncol * p.ow; it += 256) {        // (column origin, output pixel)
+        const int col = it >= p.ow, ox = it - col * p.ow;
+        const int32_t *xe = xt + ox * (2 + p.xtaps);
+        const int xmin = xe[0], xn = xe[1];
+        const float *wx = reinterpret_cast<const float *>(xe + 2);
+        const float *rw = rows + ((col ? xb : xa) - x_lo + xmin) * p.C;
+        float acc[FG][3];
+#pragma unroll
+        for (int ff = 0; ff < FG; ++ff)
+#pragma unroll
+            for (int c = 0; c < 3; ++c) acc[ff][c] = 0.f;
+        for (int j = 0; j < xn; j++) {
+            const float wj = wx[j];
+            const float *r = rw + j * p.C;
+#pragma unroll
+            for (int ff = 0; ff < FG; ++ff)
+#pragma unroll
+                for (int c = 0; c < 3; ++c)
+                    if (c < p.C) acc[ff][c] += wj * r[ff * rbuf + c];
+        }
+        uint16_t *rec = reinterpret_cast<uint16_t *>(tile + col * tile8) + ((size_t)((ox & 1) * wq_n + (ox >> 1))) * 12;
+#pragma unroll
+        for (int ff = 0; ff < FG; ++ff) {
+            if (!live[ff]) continue;
+#pragma unroll
+            for (int c = 0; c < 3; ++c) rec[ff * 3 + c] = c < p.C ? T::from_f32(acc[ff][c]) : (uint16_t)0;
+        }
+    }
+    __syncthreads();
+    // crops of this row origin: ka from origin a, ka + 1 from origin b (corners), 5 + ka = the mirror of origin b, 5 + ka + 1 = the mirror of origin a (corners)
+    const int ka = grp == 0 ? 0 : grp == 1 ? 4 : 2;
+    const uint2 *ta = tile, *tb = tile + (ncol - 1) * tile8;
+    const int nrec = 2 * wq_n;
+    const bool corner = grp != 1;
+    const long clip8 = (long)q.tp_n * p.oh * nrec * 6;               // a clip's records in 8-byte pieces
+    uint2 *dst[2];                                                   // this row of crop 0, pair qd (first halves) and pair qd - 1 (second halves)
+    bool on[2];
+#pragma unroll
+    for (int half = 0; half < 2; ++half) {
+        const int tp = qd - half;
+        on[half] = tp >= 0 && tp < q.tp_n;                           // uniform
+        dst[half] = reinterpret_cast<uint2 *>(q.rec) + (long)n * 10 * clip8 + (((long)(on[half] ? tp : 0) * p.oh + oy) * (long)nrec) * 6 + half * 3;
+    }
+    // a piece is read once per tile and order and leaves for both pairs: four loads from LDS in flight, then up to eight stores
+    for (int i = threadIdx.x; i < tile8; i += 256) {
+        const int rc = i / 3, pc = i - rc * 3, mi = (nrec - 1 - rc) * 3 + pc;
+        const uint2 va = ta[i], vbm = tb[mi];
+        uint2 vb = va, vam = vbm;
+        if (corner) {
+            vb = tb[i];
+            vam = ta[mi];
+        }
+        const long o = (long)rc * 6 + pc;
+#pragma unroll
+        for (int half = 0; half < 2; ++half) {
+            if (!on[half]) continue;
+            uint2 *d = dst[half] + o;
+            d[ka * clip8] = va;
+            d[(5 + ka) * clip8] = vbm;
+            if (corner) {
+                d[(ka + 1) * clip8] = vb;
+                d[(6 + ka) * clip8] = vam;
+            }
+        }
+    }
+}
+
 // ------------------------------------------------------------------------------------------------------------
 // uint8 frames -> crop box -> Pillow's two-pass BILINEAR resize (8-bit intermediate image) -> /255 -> fp32:
 // `shanghai_frames_dataset.augmentation` (feature_extraction/shanghai_dl.py:27-40: to_pil_image, center_crop, resize(antialias),
@@ -531,6 +699,43 @@ extern "C" int32_t tedspad_frames_crop_resize_tp(const void *frames, int32_t in_
     const char *who = "tedspad_frames_crop_resize_tp";      // (wide source frames (HD) need more than the default 64 KB of dynamic LDS)
     if (in_is_float) TS_WITH_T(dtype, return launch_lds<crop_resize_tp_kernel<float, T>>(who, g, dim3(256), lds, s, q));
     TS_WITH_T(dtype, return launch_lds<crop_resize_tp_kernel<uint8_t, T>>(who, g, dim3(256), lds, s, q));
+}
+
+extern "C" int32_t tedspad_frames_ten_crop_tp(const void *frames, int32_t in_is_float, int32_t T, int32_t H, int32_t W, int32_t C, int32_t n_clips,
+                                              int32_t first, int32_t clip_step, int32_t frame_step, int32_t t_clip, int32_t ch, int32_t cw, int32_t yc,
+                                              int32_t xc, int32_t oh, int32_t ow, const int32_t *ytab, const int32_t *xtab, float divisor, void *records,
+                                              int32_t pad_t, int32_t stride_t, int32_t t_pairs, int32_t dtype, void *stream) {
+    TS_REQUIRE(frames && records && ytab && xtab, "tedspad_frames_ten_crop_tp: null pointer");
+    TS_REQUIRE(T > 0 && H > 0 && W > 0 && C > 0 && C <= 3 && oh > 0 && ow > 0 && ow % 2 == 0, "tedspad_frames_ten_crop_tp: bad sizes (<= 3 channels, even output width)");
+    TS_REQUIRE(n_clips > 0 && t_clip > 0 && frame_step > 0 && clip_step >= 0, "tedspad_frames_ten_crop_tp: bad clip sampling");
+    TS_REQUIRE(ch > 0 && cw > 0 && ch <= H && cw <= W, "tedspad_frames_ten_crop_tp: crop %dx%d larger than the %dx%d frame", ch, cw, H, W);
+    TS_REQUIRE(yc >= 0 && xc >= 0 && yc + ch <= H && xc + cw <= W,
+               "tedspad_frames_ten_crop_tp: centre crop box (%d,%d,%d,%d) outside the %dx%d frame", yc, xc, ch, cw, H, W);
+    TS_REQUIRE(divisor != 0.f, "tedspad_frames_ten_crop_tp: divisor must be non-zero");
+    TS_REQUIRE(stride_t == 2 && pad_t >= 0 && t_pairs > 0, "tedspad_frames_ten_crop_tp: temporal stride 2 (tedspad_clip_to_tp's record layout)");
+    TS_REQUIRE(dtype == TEDSPAD_F16 || dtype == TEDSPAD_BF16, "tedspad_frames_ten_crop_tp: bad dtype");
+    const long nblk = 3L * n_clips * oh * (t_pairs + 1), per = 8L * (t_pairs + 1);      // (clip time, output row, row origin, frame quad)
+    TS_REQUIRE((uintptr_t)records % 16 == 0 && nblk + per < (1L << 31), "tedspad_frames_ten_crop_tp: records must be 16-byte aligned; too many rows");
+    // two rows of half records (one per column origin) + four frames' full-width row buffers + the value table
+    const size_t lds = (size_t)ow * 48 + (size_t)4 * W * C * sizeof(float) + 1024;
+    TS_REQUIRE(lds <= 160 * 1024, "tedspad_frames_ten_crop_tp: %d columns of records + four %d x %d row buffers exceed the CU's 160 KB of LDS", ow, W, C);
+    TenCropKP kp;
+    ResizeTpKP &q = kp.q;
+    ResizeKP &p = q.r;
+    p.in = frames; p.out = nullptr; p.ytab = ytab; p.xtab = xtab;
+    p.T = T; p.H = H; p.W = W; p.C = C; p.y0 = 0; p.x0 = 0; p.ch = ch; p.cw = cw; p.oh = oh; p.ow = ow;
+    p.ytaps = aa_taps(ch, oh); p.xtaps = aa_taps(cw, ow); p.flip = 0; p.div = divisor;
+    p.so_t = p.so_c = p.so_h = p.so_w = 0;
+    q.rec = (uint16_t *)records; q.n_clips = n_clips; q.first = first; q.clip_step = clip_step; q.frame_step = frame_step; q.t_clip = t_clip;
+    q.pt = pad_t; q.stt = stride_t; q.tp_n = t_pairs;
+    q.in_end = (const uint8_t *)frames + (size_t)T * H * W * C * (in_is_float ? 4 : 1);
+    kp.yc = yc; kp.xc = xc;
+    hipStream_t s = (hipStream_t)stream;
+    kp.nblk = (int)nblk;
+    const dim3 g((unsigned)((nblk + per - 1) / per * per));          // whole rounds of 8 x (t_pairs + 1) blocks: the kernel's block order
+    const char *who = "tedspad_frames_ten_crop_tp";
+    if (in_is_float) TS_WITH_T(dtype, return launch_lds<ten_crop_tp_kernel<float, T>>(who, g, dim3(256), lds, s, kp));
+    TS_WITH_T(dtype, return launch_lds<ten_crop_tp_kernel<uint8_t, T>>(who, g, dim3(256), lds, s, kp));
 }
 
 // the checks the two activation entries share; fills the output description

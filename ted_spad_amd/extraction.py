@@ -178,16 +178,62 @@ def extract_video_sharded(ft_model, clips_local: torch.Tensor, T: int, ncrops: i
     return sharding.gather_video_features(f, T, group)
 
 
+def _extract_video_ten_crop(ft_model, net, frames, crop_hw, out_hw, clip_step, frame_step, t_clip, n_clips, batch, streams, out):
+    """extract_video_features_uint8(crops=10): (n_clips, 10, F), `max(1, batch // 10)` clip times (x 10 crops, crop-minor) per forward."""
+    from . import engine as E, preprocess
+    t, h, w, c = frames.shape
+    dev, fw = frames.device, feature_width(ft_model)
+    if out is None:
+        out = torch.empty((n_clips, 10, fw), dtype=torch.float32, device=dev)
+    if tuple(out.shape) != (n_clips, 10, fw) or out.dtype != torch.float32 or out.device != dev or not out.is_contiguous():
+        raise ValueError("extract_video_features_uint8: with crops=10 out must be contiguous fp32 (%d, 10, %d) on %s" % (n_clips, fw, dev))
+    if n_clips == 0:
+        return out
+    boxes = preprocess.ten_crop_boxes(h, w, crop_hw[0], crop_hw[1])
+    rows = out.view(n_clips * 10, fw)
+    pool = _STREAMS.setdefault((dev, streams), [torch.cuda.Stream(device=dev) for _ in range(max(1, streams))])
+    main = torch.cuda.current_stream(dev)
+    for st in pool:
+        st.wait_stream(main)
+    rec_path = hasattr(net, "extract_features_records") and E.STEM_PT and E.STEM_POOL
+    stem = net.packed()["stem_pt"] if rec_path else None
+    # batch_plan in clip times: a forward per stream as long as each keeps 4 clip times (40 clips; 32 with one crop)
+    for j, (i, k) in enumerate(sharding.batch_plan(n_clips, max(1, batch // 10), len(pool), min_batch=4)):
+        with torch.cuda.stream(pool[0 if E.tuning_pending() else j % len(pool)]):
+            if rec_path:
+                rec = preprocess.ten_crop_records(frames, crop_hw, out_hw, stem, k, first=i * clip_step, clip_step=clip_step, frame_step=frame_step, t_clip=t_clip)
+                rows[10 * i:10 * (i + k)] = net.extract_features_records(rec).flatten(1)
+            else:
+                clips = torch.zeros((10 * k, c, t_clip, out_hw[0], out_hw[1]), dtype=torch.float32, device=dev)
+                for q in range(k):
+                    f0 = (i + q) * clip_step
+                    idx = [f0 + f * frame_step for f in range(t_clip) if f0 + f * frame_step < t]
+                    if idx:
+                        sel = frames[idx[0]:idx[-1] + 1:frame_step].contiguous()
+                        for cr, b in enumerate(boxes):
+                            preprocess.crop_resize(sel, b[:4], out_hw, flip=b[4], out=clips[10 * q + cr, :, :len(idx)], layout="cthw")
+                rows[10 * i:10 * (i + k)] = _extract_fn(ft_model)(clips).flatten(1)
+    for st in pool:
+        main.wait_stream(st)
+    return out
+
+
 @torch.no_grad()
 def extract_video_features_uint8(ft_model, frames: torch.Tensor, cropping_factor: float = 0.8, no_ar_distortion: bool = False, out_hw=(224, 224),
                                  clip_step: int = 32, frame_step: int = 2, t_clip: int = 16, n_clips: int = None, batch: int = 375, streams: int = 2,
-                                 out: torch.Tensor = None) -> torch.Tensor:
+                                 out: torch.Tensor = None, crops: int = 1) -> torch.Tensor:
     """The whole per-video path of dali_extraction.py without its anonymizer, from DECODED FRAMES: frames (T,H,W,3) uint8 (or the float frames DALI hands
     over) resident on the GPU -> HybridValPipe's clip sampling (:62-73: 16 frames, every 2nd, a clip per 32 source frames; frames past the end are zero
     frames) -> val_augmentations (:38-50: /255, centre crop 0.8, antialiased resize) -> I3Res50.extract_features -> (n_clips, F) fp32 rows on the GPU.
     Pre-processing writes the persistent stem's 16-bit input records directly (preprocess.crop_resize_records -> I3Res50.extract_features_records): ONE launch
-    per batch in front of the encoder, no fp32 clip batch in HBM. Encoders without the record path (InceptionI3d) take the fp32 clips."""
+    per batch in front of the encoder, no fp32 clip batch in HBM. Encoders without the record path (InceptionI3d) take the fp32 clips.
+
+    crops=10: val_augmentations with its center_crop replaced by torchvision's ten_crop of the same crop size (preprocess.ten_crop_boxes' order) ->
+    (n_clips, 10, F), the block MGFN's loader takes (mgfn_feed.getitem); [:, 4] is the crops=1 result. `max(1, batch // 10)` clip times per forward (about
+    `batch` clips, as with one crop), their records from ONE launch (preprocess.ten_crop_records)."""
     from . import engine as E, preprocess
+    if crops not in (1, 10):
+        raise ValueError("extract_video_features_uint8: crops must be 1 (centre crop) or 10 (ten_crop), got %r" % (crops,))
     E.require_cuda(frames, "extract_video_features_uint8")
     net = ft_model.i3d if hasattr(ft_model, "i3d") else ft_model
     t, h, w, c = frames.shape
@@ -197,6 +243,8 @@ def extract_video_features_uint8(ft_model, frames: torch.Tensor, cropping_factor
         ch = cw = int(min(h, w) * cropping_factor)
     else:
         ch, cw = int(h * cropping_factor), int(w * cropping_factor)
+    if crops == 10:
+        return _extract_video_ten_crop(ft_model, net, frames, (ch, cw), out_hw, clip_step, frame_step, t_clip, n_clips, batch, streams, out)
     box = preprocess.center_crop_box(h, w, ch, cw)
     if out is None:
         out = torch.empty((n_clips, feature_width(ft_model)), dtype=torch.float32, device=frames.device)
@@ -267,7 +315,7 @@ def anonymized_video_clips(t: int, resample: str = "aa", first: int = 0, clip_st
 def extract_anonymized_video_features_uint8(ft_model, fa_model, frames: torch.Tensor, cropping_factor: float = 0.8, no_ar_distortion: bool = False,
                                             out_hw=(224, 224), clip_step: int = 32, frame_step: int = 2, t_clip: int = 16, first: int = 0, n_clips: int = None,
                                             batch: int = 75, fa_batch: int = 75, layout: str = "reference", resample: str = "aa", streams: int = 2,
-                                            out: torch.Tensor = None) -> torch.Tensor:
+                                            out: torch.Tensor = None, crops: int = 1) -> torch.Tensor:
     """The per-video path the reference's two extraction scripts really run (`anonymized = True` is hard-coded: dali_extraction.py:108,169-178,
     st_feature_extraction.py:24-30), from DECODED FRAMES resident on the GPU: frames (T,H,W,3) uint8 (resample 'aa': or the float frames DALI hands over) ->
     clip sampling (clip i, frame f = source frame first + i*clip_step + f*frame_step) -> per frame / 255, centre crop, resize -> fa on every frame -> the Q1
@@ -281,8 +329,15 @@ def extract_anonymized_video_features_uint8(ft_model, fa_model, frames: torch.Te
 
     Per `fa_batch` clips ONE launch (preprocess.crop_resize_act) writes the 16-bit channels-last activation fa's first conv reads and `fa_model.forward_act`
     starts from it: no fp32 frame batch is written or read back, and the rows are bit-identical to `extract_anonymized_clip_features` on the fp32 clips.
-    `batch` clips per encoder forward, the batches alternating over `streams` HIP streams. `fa_model`: UnetPlusPlus or UNet."""
+    `batch` clips per encoder forward, the batches alternating over `streams` HIP streams. `fa_model`: UnetPlusPlus or UNet.
+
+    crops=10 (resample 'aa' only: the Pillow path has no flip): the centre crop replaced by torchvision's ten_crop of the same size -> (n_clips, 10, F), crop k
+    of `preprocess.ten_crop_boxes` in [:, k]; each crop runs the pipeline above on its (box, flip), so [:, 4] is the crops=1 result."""
     from . import engine as E, preprocess
+    if crops not in (1, 10):
+        raise ValueError("extract_anonymized_video_features_uint8: crops must be 1 (centre crop) or 10 (ten_crop), got %r" % (crops,))
+    if crops == 10 and resample != "aa":
+        raise ValueError("extract_anonymized_video_features_uint8: crops=10 needs resample='aa' (the Pillow path has no flip), got %r" % (resample,))
     if not hasattr(fa_model, "forward_act"):
         raise TypeError("extract_anonymized_video_features_uint8: fa_model %s has no forward_act (UnetPlusPlus and UNet start from the 16-bit activation)"
                         % type(fa_model).__name__)
@@ -298,36 +353,45 @@ def extract_anonymized_video_features_uint8(ft_model, fa_model, frames: torch.Te
         n_clips = anonymized_video_clips(t, resample, first, clip_step, frame_step, t_clip)
     oh, ow = int(out_hw[0]), int(out_hw[1])
     dev = frames.device
+    shape = (n_clips, feature_width(ft_model)) if crops == 1 else (n_clips, 10, feature_width(ft_model))
     if out is None:
-        out = torch.empty((n_clips, feature_width(ft_model)), dtype=torch.float32, device=dev)
-    if tuple(out.shape) != (n_clips, feature_width(ft_model)) or out.dtype != torch.float32 or out.device != dev:
-        raise ValueError("extract_anonymized_video_features_uint8: out must be fp32 (%d, %d) on %s" % (n_clips, feature_width(ft_model), dev))
+        out = torch.empty(shape, dtype=torch.float32, device=dev)
+    if tuple(out.shape) != shape or out.dtype != torch.float32 or out.device != dev:
+        raise ValueError("extract_anonymized_video_features_uint8: out must be fp32 %s on %s" % (shape, dev))
     if n_clips == 0:
         return out
     cpad, dt = fa_model.ACT_CPAD, fa_model.compute_dtype
     fa_step = fa_batch if fa_batch else batch
+    # (box, flip, rows): the centre crop into out, or crop k of ten_crop (the centre crop's size) into out[:, k]
+    if crops == 1:
+        jobs = [(box, False, out)]
+    else:
+        jobs = [(b[:4], b[4], out[:, k]) for k, b in enumerate(preprocess.ten_crop_boxes(h, w, box[2], box[3]))]
 
-    def anonymized(i, k):       # clips i .. i + k - 1 -> fa's output frames (k * t_clip, c, oh, ow) fp32
-        act = preprocess.crop_resize_act(frames, box, (oh, ow), k, first=first + i * clip_step, clip_step=clip_step, frame_step=frame_step, t_clip=t_clip,
-                                         cpad=cpad, dtype=dt, resample=resample)
+    def anonymized(i, k, cbox, flip):       # clips i .. i + k - 1 -> fa's output frames (k * t_clip, c, oh, ow) fp32
+        act = preprocess.crop_resize_act(frames, cbox, (oh, ow), k, first=first + i * clip_step, clip_step=clip_step, frame_step=frame_step, t_clip=t_clip,
+                                         cpad=cpad, dtype=dt, flip=flip, resample=resample)
         return fa_model.forward_act(act)
 
     pool = _STREAMS.setdefault((dev, streams), [torch.cuda.Stream(device=dev) for _ in range(max(1, streams))])
     main = torch.cuda.current_stream(dev)
     for st in pool:
         st.wait_stream(main)
-    for j, i in enumerate(range(0, n_clips, batch)):
-        b = min(batch, n_clips - i)
-        with torch.cuda.stream(pool[0 if E.tuning_pending() else j % len(pool)]):
-            if b > fa_step:
-                fr = torch.empty((b * t_clip, c, oh, ow), dtype=torch.float32, device=dev)
-                for q in range(0, b, fa_step):
-                    k = min(fa_step, b - q)
-                    fr[q * t_clip:(q + k) * t_clip] = anonymized(i + q, k)
-            else:
-                fr = anonymized(i, b)
-            x = fr.reshape(b, c, t_clip, oh, ow) if layout == "reference" else fr.reshape(b, t_clip, c, oh, ow).permute(0, 2, 1, 3, 4)
-            out[i:i + b] = fx(x).flatten(1)
+    j = 0
+    for cbox, flip, rows in jobs:
+        for i in range(0, n_clips, batch):
+            b = min(batch, n_clips - i)
+            with torch.cuda.stream(pool[0 if E.tuning_pending() else j % len(pool)]):
+                if b > fa_step:
+                    fr = torch.empty((b * t_clip, c, oh, ow), dtype=torch.float32, device=dev)
+                    for q in range(0, b, fa_step):
+                        k = min(fa_step, b - q)
+                        fr[q * t_clip:(q + k) * t_clip] = anonymized(i + q, k, cbox, flip)
+                else:
+                    fr = anonymized(i, b, cbox, flip)
+                x = fr.reshape(b, c, t_clip, oh, ow) if layout == "reference" else fr.reshape(b, t_clip, c, oh, ow).permute(0, 2, 1, 3, 4)
+                rows[i:i + b] = fx(x).flatten(1)
+            j += 1
     for st in pool:
         main.wait_stream(st)
     warn_if_saturated(ft_model)

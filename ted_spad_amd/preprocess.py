@@ -57,7 +57,8 @@ def center_crop_box(h: int, w: int, ch: int, cw: int):
 def ten_crop_boxes(h: int, w: int, ch: int, cw: int):
     """torchvision ten_crop order (tl, tr, bl, br, center, then the same five of the horizontally flipped frame) as
     (y0, x0, ch, cw, flip) boxes in the coordinates of the UNFLIPPED frame. Not used by the reference's extractor
-    (single centre crop); provided for the (T,10,F) layout its MGFN loader accepts (dataset.py:70-89)."""
+    (single centre crop); provided for the (T,10,F) layout its MGFN loader accepts (dataset.py:70-89): the `crops=10` form of the extraction drivers,
+    `ten_crop_records`."""
     five = [(0, 0), (0, w - cw), (h - ch, 0), (h - ch, w - cw), center_crop_box(h, w, ch, cw)[:2]]
     out = [(y, x, ch, cw, False) for y, x in five]
     out += [(y, w - cw - x, ch, cw, True) for y, x in five]
@@ -113,6 +114,34 @@ def crop_resize_records(frames: torch.Tensor, box, out_hw, stem, n_clips: int, f
                                                    int(frame_step), int(t_clip), y0, x0, ch, cw, oh, ow, ytab.data_ptr(), xtab.data_ptr(), C.c_float(divisor),
                                                    int(flip), out.data_ptr(), stem.pad_t, stem.stride_t, tp, stem.dtype_code, _stream_ptr()),
           "tedspad_frames_crop_resize_tp")
+    return out
+
+
+def ten_crop_records(frames: torch.Tensor, crop_hw, out_hw, stem, n_clips: int, first: int = 0, clip_step: int = 32, frame_step: int = 2,
+                     t_clip: int = 16, out: torch.Tensor = None, divisor: float = 255.0) -> torch.Tensor:
+    """`crop_resize_records` for torchvision's ten_crop of size `crop_hw` = (ch, cw) in place of one box: the records (10*n_clips, tp, oh, 2, ow/2, 24) of all
+    ten crops of every clip in ONE launch, clip time i / crop k at index 10*i + k (crop-minor, what `feats.view(-1, 10, F)` expects), k in `ten_crop_boxes`'
+    order. Bit-identical to the ten `crop_resize_records(frames, box, ..., flip=flip)` launches over `ten_crop_boxes(h, w, ch, cw)` it replaces: the kernel
+    resamples vertically once per row origin and horizontally once per distinct box, and writes a flipped crop as its box's values right to left."""
+    require_cuda(frames, "ten_crop_records")
+    if frames.dim() != 4 or frames.dtype not in (torch.uint8, torch.float32) or not frames.is_contiguous():
+        raise ValueError("ten_crop_records: frames must be a contiguous (T,H,W,C) uint8/float32 tensor")
+    t, h, w, c = frames.shape
+    ch, cw = int(crop_hw[0]), int(crop_hw[1])
+    oh, ow = int(out_hw[0]), int(out_hw[1])
+    tp = stem.frame_pairs(t_clip)
+    shape = (10 * n_clips, tp, oh, 2, ow // 2, 24)
+    if out is None:
+        out = torch.empty(shape, dtype=stem.torch_dtype, device=frames.device)
+    if tuple(out.shape) != shape or out.dtype != stem.torch_dtype or not out.is_contiguous():
+        raise ValueError("ten_crop_records: out must be a contiguous %s tensor of %s" % (shape, stem.torch_dtype))
+    # the centre origin by the one rule (half to even); a crop larger than the frame goes to the entry, which refuses it as it refuses crop_resize_records' box
+    yc, xc = center_crop_box(h, w, ch, cw)[:2] if ch <= h and cw <= w else (0, 0)
+    ytab, xtab = _table(ch, oh, frames.device), _table(cw, ow, frames.device)
+    check(_lib.lib().tedspad_frames_ten_crop_tp(frames.data_ptr(), int(frames.dtype == torch.float32), t, h, w, c, int(n_clips), int(first), int(clip_step),
+                                                int(frame_step), int(t_clip), ch, cw, yc, xc, oh, ow, ytab.data_ptr(), xtab.data_ptr(), C.c_float(divisor),
+                                                out.data_ptr(), stem.pad_t, stem.stride_t, tp, stem.dtype_code, _stream_ptr()),
+          "tedspad_frames_ten_crop_tp")
     return out
 
 
