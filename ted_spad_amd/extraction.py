@@ -11,6 +11,7 @@ config writes.
 """
 from __future__ import annotations
 
+import contextlib
 import os
 
 import numpy as np
@@ -63,6 +64,21 @@ def feed(clips: torch.Tensor, fa_model=None, layout: str = "reference", fa_batch
 _STREAMS = {}
 
 
+@contextlib.contextmanager
+def _stream_pool(dev, streams: int):
+    """The drivers' fork and join: the pool of `streams` HIP streams waits for the current stream, the body runs job j under `on(j)` -- the pool's stream
+    j % streams -- and the current stream waits for the pool. Yields (streams, on)."""
+    from . import engine as E
+    pool = _STREAMS.setdefault((dev, streams), [torch.cuda.Stream(device=dev) for _ in range(max(1, streams))])
+    main = torch.cuda.current_stream(dev)
+    for st in pool:
+        st.wait_stream(main)
+    # while the conv tile tuner is still timing candidates, stay on one stream (engine.tuning_pending)
+    yield len(pool), lambda j: torch.cuda.stream(pool[0 if E.tuning_pending() else j % len(pool)])
+    for st in pool:
+        main.wait_stream(st)
+
+
 @torch.no_grad()
 def extract_clip_features(ft_model, clips_cthw: torch.Tensor, batch: int = 75, out: torch.Tensor = None, streams: int = 3) -> torch.Tensor:
     """clips_cthw: (n, 3, T, H, W) fp32 on the GPU -> (n, F) fp32 on the GPU, `batch` clips per forward.
@@ -80,18 +96,11 @@ def extract_clip_features(ft_model, clips_cthw: torch.Tensor, batch: int = 75, o
             f = fx(clips_cthw[i:i + batch]).flatten(1)
             out[i:i + f.shape[0]] = f
         return out
-    pool = _STREAMS.setdefault((dev, streams), [torch.cuda.Stream(device=dev) for _ in range(max(1, streams))])
-    main = torch.cuda.current_stream(dev)
-    for st in pool:
-        st.wait_stream(main)
-    from . import engine as E
-    # forwards of at most `batch` clips, spread evenly over the streams (a 290-clip shard of a video split over 8 ranks: 145 + 145, not 290 on one stream)
-    for j, (i, k) in enumerate(sharding.batch_plan(n, batch, len(pool))):
-        # while the conv tile tuner is still timing candidates, stay on one stream (engine.tuning_pending)
-        with torch.cuda.stream(pool[0 if E.tuning_pending() else j % len(pool)]):
-            out[i:i + k] = fx(clips_cthw[i:i + k]).flatten(1)
-    for st in pool:
-        main.wait_stream(st)
+    with _stream_pool(dev, streams) as (n_streams, on):
+        # forwards of at most `batch` clips, spread evenly over the streams (a 290-clip shard of a video split over 8 ranks: 145 + 145, not 290 on one stream)
+        for j, (i, k) in enumerate(sharding.batch_plan(n, batch, n_streams)):
+            with on(j):
+                out[i:i + k] = fx(clips_cthw[i:i + k]).flatten(1)
     return out
 
 
@@ -113,17 +122,11 @@ def extract_anonymized_clip_features(ft_model, fa_model, clips: torch.Tensor, ba
             f = fx(feed(clips[i:i + batch], fa_model, layout, fa_batch=fa_batch)).flatten(1)
             out[i:i + f.shape[0]] = f
         return out
-    pool = _STREAMS.setdefault((dev, streams), [torch.cuda.Stream(device=dev) for _ in range(max(1, streams))])
-    main = torch.cuda.current_stream(dev)
-    for st in pool:
-        st.wait_stream(main)
-    from . import engine as E
-    for j, i in enumerate(range(0, n, batch)):
-        with torch.cuda.stream(pool[0 if E.tuning_pending() else j % len(pool)]):
-            f = fx(feed(clips[i:i + batch], fa_model, layout, fa_batch=fa_batch)).flatten(1)
-            out[i:i + f.shape[0]] = f
-    for st in pool:
-        main.wait_stream(st)
+    with _stream_pool(dev, streams) as (_, on):
+        for j, i in enumerate(range(0, n, batch)):
+            with on(j):
+                f = fx(feed(clips[i:i + batch], fa_model, layout, fa_batch=fa_batch)).flatten(1)
+                out[i:i + f.shape[0]] = f
     return out
 
 
@@ -178,44 +181,20 @@ def extract_video_sharded(ft_model, clips_local: torch.Tensor, T: int, ncrops: i
     return sharding.gather_video_features(f, T, group)
 
 
-def _extract_video_ten_crop(ft_model, net, frames, crop_hw, out_hw, clip_step, frame_step, t_clip, n_clips, batch, streams, out):
-    """extract_video_features_uint8(crops=10): (n_clips, 10, F), `max(1, batch // 10)` clip times (x 10 crops, crop-minor) per forward."""
-    from . import engine as E, preprocess
-    t, h, w, c = frames.shape
-    dev, fw = frames.device, feature_width(ft_model)
-    if out is None:
-        out = torch.empty((n_clips, 10, fw), dtype=torch.float32, device=dev)
-    if tuple(out.shape) != (n_clips, 10, fw) or out.dtype != torch.float32 or out.device != dev or not out.is_contiguous():
-        raise ValueError("extract_video_features_uint8: with crops=10 out must be contiguous fp32 (%d, 10, %d) on %s" % (n_clips, fw, dev))
-    if n_clips == 0:
-        return out
-    boxes = preprocess.ten_crop_boxes(h, w, crop_hw[0], crop_hw[1])
-    rows = out.view(n_clips * 10, fw)
-    pool = _STREAMS.setdefault((dev, streams), [torch.cuda.Stream(device=dev) for _ in range(max(1, streams))])
-    main = torch.cuda.current_stream(dev)
-    for st in pool:
-        st.wait_stream(main)
-    rec_path = hasattr(net, "extract_features_records") and E.STEM_PT and E.STEM_POOL
-    stem = net.packed()["stem_pt"] if rec_path else None
-    # batch_plan in clip times: a forward per stream as long as each keeps 4 clip times (40 clips; 32 with one crop)
-    for j, (i, k) in enumerate(sharding.batch_plan(n_clips, max(1, batch // 10), len(pool), min_batch=4)):
-        with torch.cuda.stream(pool[0 if E.tuning_pending() else j % len(pool)]):
-            if rec_path:
-                rec = preprocess.ten_crop_records(frames, crop_hw, out_hw, stem, k, first=i * clip_step, clip_step=clip_step, frame_step=frame_step, t_clip=t_clip)
-                rows[10 * i:10 * (i + k)] = net.extract_features_records(rec).flatten(1)
-            else:
-                clips = torch.zeros((10 * k, c, t_clip, out_hw[0], out_hw[1]), dtype=torch.float32, device=dev)
-                for q in range(k):
-                    f0 = (i + q) * clip_step
-                    idx = [f0 + f * frame_step for f in range(t_clip) if f0 + f * frame_step < t]
-                    if idx:
-                        sel = frames[idx[0]:idx[-1] + 1:frame_step].contiguous()
-                        for cr, b in enumerate(boxes):
-                            preprocess.crop_resize(sel, b[:4], out_hw, flip=b[4], out=clips[10 * q + cr, :, :len(idx)], layout="cthw")
-                rows[10 * i:10 * (i + k)] = _extract_fn(ft_model)(clips).flatten(1)
-    for st in pool:
-        main.wait_stream(st)
-    return out
+def _fp32_clips(frames, boxes, out_hw, i, k, clip_step, frame_step, t_clip):
+    """Encoders without the record path: the fp32 clips (k * len(boxes), C, t_clip, oh, ow) of clip times i .. i + k - 1, one per (y0, x0, ch, cw, flip) of
+    `boxes`, crop-minor; frames past the end of the video stay zero."""
+    from . import preprocess
+    t, c, nb = frames.shape[0], frames.shape[3], len(boxes)
+    clips = torch.zeros((nb * k, c, t_clip, out_hw[0], out_hw[1]), dtype=torch.float32, device=frames.device)
+    for q in range(k):
+        f0 = (i + q) * clip_step
+        idx = [f0 + f * frame_step for f in range(t_clip) if f0 + f * frame_step < t]
+        if idx:
+            sel = frames[idx[0]:idx[-1] + 1:frame_step].contiguous()
+            for cr, b in enumerate(boxes):
+                preprocess.crop_resize(sel, b[:4], out_hw, flip=b[4], out=clips[nb * q + cr, :, :len(idx)], layout="cthw")
+    return clips
 
 
 @torch.no_grad()
@@ -239,40 +218,34 @@ def extract_video_features_uint8(ft_model, frames: torch.Tensor, cropping_factor
     t, h, w, c = frames.shape
     if n_clips is None:
         n_clips = -(-t // clip_step)
-    if no_ar_distortion:
-        ch = cw = int(min(h, w) * cropping_factor)
+    ch, cw = preprocess.val_crop_size(h, w, cropping_factor, no_ar_distortion)
+    dev, fw = frames.device, feature_width(ft_model)
+    # `crops` selects the (box, flip) list, the record builder with its geometry argument, and the rows of `out` a clip time fills (crop-minor)
+    if crops == 1:
+        boxes = [preprocess.center_crop_box(h, w, ch, cw) + (False,)]
+        records, geom, shape = preprocess.crop_resize_records, boxes[0][:4], (n_clips, fw)
     else:
-        ch, cw = int(h * cropping_factor), int(w * cropping_factor)
-    if crops == 10:
-        return _extract_video_ten_crop(ft_model, net, frames, (ch, cw), out_hw, clip_step, frame_step, t_clip, n_clips, batch, streams, out)
-    box = preprocess.center_crop_box(h, w, ch, cw)
+        boxes = preprocess.ten_crop_boxes(h, w, ch, cw)
+        records, geom, shape = preprocess.ten_crop_records, (ch, cw), (n_clips, 10, fw)
     if out is None:
-        out = torch.empty((n_clips, feature_width(ft_model)), dtype=torch.float32, device=frames.device)
+        out = torch.empty(shape, dtype=torch.float32, device=dev)
+    if crops == 10 and (tuple(out.shape) != shape or out.dtype != torch.float32 or out.device != dev or not out.is_contiguous()):
+        raise ValueError("extract_video_features_uint8: with crops=10 out must be contiguous fp32 (%d, 10, %d) on %s" % (n_clips, fw, dev))
     if n_clips == 0:
         return out
-    dev = frames.device
-    pool = _STREAMS.setdefault((dev, streams), [torch.cuda.Stream(device=dev) for _ in range(max(1, streams))])
-    main = torch.cuda.current_stream(dev)
-    for st in pool:
-        st.wait_stream(main)
+    rows = out if crops == 1 else out.view(n_clips * 10, fw)
     rec_path = hasattr(net, "extract_features_records") and E.STEM_PT and E.STEM_POOL
     stem = net.packed()["stem_pt"] if rec_path else None
-    for j, (i, k) in enumerate(sharding.batch_plan(n_clips, batch, len(pool))):
-        with torch.cuda.stream(pool[0 if E.tuning_pending() else j % len(pool)]):
-            if rec_path:
-                rec = preprocess.crop_resize_records(frames, box, out_hw, stem, k, first=i * clip_step, clip_step=clip_step, frame_step=frame_step, t_clip=t_clip)
-                out[i:i + k] = net.extract_features_records(rec).flatten(1)
-            else:
-                clips = torch.zeros((k, c, t_clip, out_hw[0], out_hw[1]), dtype=torch.float32, device=dev)
-                for q in range(k):
-                    f0 = (i + q) * clip_step
-                    idx = [f0 + f * frame_step for f in range(t_clip) if f0 + f * frame_step < t]
-                    if idx:
-                        sel = frames[idx[0]:idx[-1] + 1:frame_step].contiguous()
-                        preprocess.crop_resize(sel, box, out_hw, out=clips[q, :, :len(idx)], layout="cthw")
-                out[i:i + k] = _extract_fn(ft_model)(clips).flatten(1)
-    for st in pool:
-        main.wait_stream(st)
+    with _stream_pool(dev, streams) as (n_streams, on):
+        # batch_plan in clip times, about `batch` clips per forward: a forward per stream as long as each keeps 4 clip times (40 clips; 32 with one crop)
+        for j, (i, k) in enumerate(sharding.batch_plan(n_clips, batch if crops == 1 else max(1, batch // 10), n_streams,min_batch=32 if crops == 1 else 4)):
+            with on(j):
+                if rec_path:
+                    rec = records(frames, geom, out_hw, stem, k, first=i * clip_step, clip_step=clip_step, frame_step=frame_step, t_clip=t_clip)
+                    f = net.extract_features_records(rec)
+                else:
+                    f = _extract_fn(ft_model)(_fp32_clips(frames, boxes, out_hw, i, k, clip_step, frame_step, t_clip))
+                rows[crops * i:crops * (i + k)] = f.flatten(1)
     return out
 
 
@@ -282,10 +255,7 @@ def anonymized_video_box(h: int, w: int, c: int = 3, cropping_factor: float = 0.
     (shanghai_dl.py:27-35 through preprocess.shanghai_crop_size, quirks included); both through torchvision's center_crop rule (preprocess.center_crop_box)."""
     from . import preprocess
     if resample == "aa":
-        if no_ar_distortion:
-            ch = cw = int(min(h, w) * cropping_factor)
-        else:
-            ch, cw = int(h * cropping_factor), int(w * cropping_factor)
+        ch, cw = preprocess.val_crop_size(h, w, cropping_factor, no_ar_distortion)
     elif resample == "pil":
         ch, cw = preprocess.shanghai_crop_size(h, w, c, cropping_factor, no_ar_distortion)
     else:
@@ -373,15 +343,10 @@ def extract_anonymized_video_features_uint8(ft_model, fa_model, frames: torch.Te
                                          cpad=cpad, dtype=dt, flip=flip, resample=resample)
         return fa_model.forward_act(act)
 
-    pool = _STREAMS.setdefault((dev, streams), [torch.cuda.Stream(device=dev) for _ in range(max(1, streams))])
-    main = torch.cuda.current_stream(dev)
-    for st in pool:
-        st.wait_stream(main)
-    j = 0
-    for cbox, flip, rows in jobs:
-        for i in range(0, n_clips, batch):
+    with _stream_pool(dev, streams) as (_, on):
+        for j, ((cbox, flip, rows), i) in enumerate((job, i) for job in jobs for i in range(0, n_clips, batch)):
             b = min(batch, n_clips - i)
-            with torch.cuda.stream(pool[0 if E.tuning_pending() else j % len(pool)]):
+            with on(j):
                 if b > fa_step:
                     fr = torch.empty((b * t_clip, c, oh, ow), dtype=torch.float32, device=dev)
                     for q in range(0, b, fa_step):
@@ -391,9 +356,6 @@ def extract_anonymized_video_features_uint8(ft_model, fa_model, frames: torch.Te
                     fr = anonymized(i, b, cbox, flip)
                 x = fr.reshape(b, c, t_clip, oh, ow) if layout == "reference" else fr.reshape(b, t_clip, c, oh, ow).permute(0, 2, 1, 3, 4)
                 rows[i:i + b] = fx(x).flatten(1)
-            j += 1
-    for st in pool:
-        main.wait_stream(st)
     warn_if_saturated(ft_model)
     return out
 

@@ -65,15 +65,36 @@ def ten_crop_boxes(h: int, w: int, ch: int, cw: int):
     return out
 
 
+def val_crop_size(h: int, w: int, factor: float = 0.8, no_ar_distortion: bool = False):
+    """`val_augmentations`' crop (ch, cw) of an (h, w) frame (dali_extraction.py:40-46): both sides times `factor`, or the square of the shorter side times it."""
+    if no_ar_distortion:
+        return (int(min(h, w) * factor),) * 2
+    return int(h * factor), int(w * factor)
+
+
+def _frames_arg(who: str, frames: torch.Tensor, pil: bool = False):
+    """The frames argument of every entry below: contiguous (T,H,W,C) on the GPU, uint8 or (not for Pillow's resample) float32. Returns (T, H, W, C)."""
+    require_cuda(frames, who)
+    if frames.dim() != 4 or frames.dtype not in ((torch.uint8,) if pil else (torch.uint8, torch.float32)) or not frames.is_contiguous():
+        raise ValueError("%s: frames must be a contiguous (T,H,W,C) %s tensor" % (who, "uint8 (PIL images are 8-bit)" if pil else "uint8/float32"))
+    return tuple(frames.shape)
+
+
+def _records_out(who: str, out: torch.Tensor, shape, stem, device) -> torch.Tensor:
+    """The `out` argument of the two record builders: a contiguous buffer of the stem's storage type to fill, or None for a new one."""
+    if out is None:
+        return torch.empty(shape, dtype=stem.torch_dtype, device=device)
+    if tuple(out.shape) != shape or out.dtype != stem.torch_dtype or not out.is_contiguous():
+        raise ValueError("%s: out must be a contiguous %s tensor of %s" % (who, shape, stem.torch_dtype))
+    return out
+
+
 def crop_resize(frames: torch.Tensor, box, out_hw, flip: bool = False, out: torch.Tensor = None, layout: str = "tchw",
                 divisor: float = 255.0) -> torch.Tensor:
     """frames: (T,H,W,C) uint8 or float32 on the GPU, contiguous. Returns / fills fp32 `out`:
     layout 'tchw' -> (T,C,oh,ow) (what val_augmentations returns), 'cthw' -> (C,T,oh,ow) (one encoder clip).
     `out` may be any strided view of the right shape (e.g. batch[i] of a (n,3,16,h,w) clip batch)."""
-    require_cuda(frames, "crop_resize")
-    if frames.dim() != 4 or frames.dtype not in (torch.uint8, torch.float32) or not frames.is_contiguous():
-        raise ValueError("crop_resize: frames must be a contiguous (T,H,W,C) uint8/float32 tensor")
-    t, h, w, c = frames.shape
+    t, h, w, c = _frames_arg("crop_resize", frames)
     y0, x0, ch, cw = [int(v) for v in box]
     oh, ow = int(out_hw[0]), int(out_hw[1])
     shape = (t, c, oh, ow) if layout == "tchw" else (c, t, oh, ow)
@@ -97,18 +118,11 @@ def crop_resize_records(frames: torch.Tensor, box, out_hw, stem, n_clips: int, f
     dali_extraction.py:62-73), each frame / divisor -> crop `box` -> antialiased resize to `out_hw` (val_augmentations, :38-50). ONE launch; the fp32 clip
     batch the encoder's public entry takes is never materialised. `stem`: the engine.StemPT of the encoder (I3Res50.packed()["stem_pt"]): temporal
     geometry and storage type. Feed the result to I3Res50.extract_features_records."""
-    require_cuda(frames, "crop_resize_records")
-    if frames.dim() != 4 or frames.dtype not in (torch.uint8, torch.float32) or not frames.is_contiguous():
-        raise ValueError("crop_resize_records: frames must be a contiguous (T,H,W,C) uint8/float32 tensor")
-    t, h, w, c = frames.shape
+    t, h, w, c = _frames_arg("crop_resize_records", frames)
     y0, x0, ch, cw = [int(v) for v in box]
     oh, ow = int(out_hw[0]), int(out_hw[1])
     tp = stem.frame_pairs(t_clip)
-    shape = (n_clips, tp, oh, 2, ow // 2, 24)
-    if out is None:
-        out = torch.empty(shape, dtype=stem.torch_dtype, device=frames.device)
-    if tuple(out.shape) != shape or out.dtype != stem.torch_dtype or not out.is_contiguous():
-        raise ValueError("crop_resize_records: out must be a contiguous %s tensor of %s" % (shape, stem.torch_dtype))
+    out = _records_out("crop_resize_records", out, (n_clips, tp, oh, 2, ow // 2, 24), stem, frames.device)
     ytab, xtab = _table(ch, oh, frames.device), _table(cw, ow, frames.device)
     check(_lib.lib().tedspad_frames_crop_resize_tp(frames.data_ptr(), int(frames.dtype == torch.float32), t, h, w, c, int(n_clips), int(first), int(clip_step),
                                                    int(frame_step), int(t_clip), y0, x0, ch, cw, oh, ow, ytab.data_ptr(), xtab.data_ptr(), C.c_float(divisor),
@@ -123,18 +137,11 @@ def ten_crop_records(frames: torch.Tensor, crop_hw, out_hw, stem, n_clips: int, 
     ten crops of every clip in ONE launch, clip time i / crop k at index 10*i + k (crop-minor, what `feats.view(-1, 10, F)` expects), k in `ten_crop_boxes`'
     order. Bit-identical to the ten `crop_resize_records(frames, box, ..., flip=flip)` launches over `ten_crop_boxes(h, w, ch, cw)` it replaces: the kernel
     resamples vertically once per row origin and horizontally once per distinct box, and writes a flipped crop as its box's values right to left."""
-    require_cuda(frames, "ten_crop_records")
-    if frames.dim() != 4 or frames.dtype not in (torch.uint8, torch.float32) or not frames.is_contiguous():
-        raise ValueError("ten_crop_records: frames must be a contiguous (T,H,W,C) uint8/float32 tensor")
-    t, h, w, c = frames.shape
+    t, h, w, c = _frames_arg("ten_crop_records", frames)
     ch, cw = int(crop_hw[0]), int(crop_hw[1])
     oh, ow = int(out_hw[0]), int(out_hw[1])
     tp = stem.frame_pairs(t_clip)
-    shape = (10 * n_clips, tp, oh, 2, ow // 2, 24)
-    if out is None:
-        out = torch.empty(shape, dtype=stem.torch_dtype, device=frames.device)
-    if tuple(out.shape) != shape or out.dtype != stem.torch_dtype or not out.is_contiguous():
-        raise ValueError("ten_crop_records: out must be a contiguous %s tensor of %s" % (shape, stem.torch_dtype))
+    out = _records_out("ten_crop_records", out, (10 * n_clips, tp, oh, 2, ow // 2, 24), stem, frames.device)
     # the centre origin by the one rule (half to even); a crop larger than the frame goes to the entry, which refuses it as it refuses crop_resize_records' box
     yc, xc = center_crop_box(h, w, ch, cw)[:2] if ch <= h and cw <= w else (0, 0)
     ytab, xtab = _table(ch, oh, frames.device), _table(cw, ow, frames.device)
@@ -152,12 +159,7 @@ def val_augmentations(video: torch.Tensor, cropping_factor: float = 0.8, no_ar_d
     if video.dim() != 5 or video.shape[0] != 1:
         raise ValueError("val_augmentations: expected (1,T,H,W,C) like the DALI reader (batch size 1)")
     _, t, h, w, c = video.shape
-    if no_ar_distortion:
-        m = min(h, w)
-        ch = cw = int(m * cropping_factor)
-    else:
-        ch, cw = int(h * cropping_factor), int(w * cropping_factor)
-    box = center_crop_box(h, w, ch, cw)
+    box = center_crop_box(h, w, *val_crop_size(h, w, cropping_factor, no_ar_distortion))
     return crop_resize(video[0].contiguous(), box, (reso_h, reso_w)).unsqueeze(0)
 
 
@@ -217,10 +219,7 @@ def _pil_table(in_size, out_size, device):
 
 def crop_resize_pil(frames: torch.Tensor, box, out_hw, out: torch.Tensor = None, layout: str = "tchw") -> torch.Tensor:
     """frames: (T,H,W,C) uint8 on the GPU -> fp32 (T,C,oh,ow) ('tchw') or (C,T,oh,ow) ('cthw'): crop + Pillow BILINEAR resize + /255."""
-    require_cuda(frames, "crop_resize_pil")
-    if frames.dim() != 4 or frames.dtype != torch.uint8 or not frames.is_contiguous():
-        raise ValueError("crop_resize_pil: frames must be a contiguous (T,H,W,C) uint8 tensor (PIL images are 8-bit)")
-    t, h, w, c = frames.shape
+    t, h, w, c = _frames_arg("crop_resize_pil", frames, pil=True)
     y0, x0, ch, cw = [int(v) for v in box]
     oh, ow = int(out_hw[0]), int(out_hw[1])
     shape = (t, c, oh, ow) if layout == "tchw" else (c, t, oh, ow)
@@ -244,17 +243,13 @@ def crop_resize_act(frames: torch.Tensor, box, out_hw, n_clips: int, first: int 
     cpad=4 -> the pixel-pair buffer (frames, 1, oh, ow/2, 8) UnetPlusPlus takes, cpad=8 -> (frames, 1, oh, ow, 8) as UNet takes it; bit-identical to it, and the
     fp32 frames are never written. resample 'aa': `crop_resize`'s arithmetic (uint8 or float32 frames); 'pil': `crop_resize_pil`'s (uint8 frames, divisor 255,
     no flip). `out`: a contiguous 16-bit buffer of that shape to fill. Feed the result to `UnetPlusPlus.forward_act` / `UNet.forward_act`."""
-    require_cuda(frames, "crop_resize_act")
     if resample not in ("aa", "pil"):
         raise ValueError("crop_resize_act: resample must be 'aa' or 'pil', got %r" % (resample,))
-    ok = (torch.uint8, torch.float32) if resample == "aa" else (torch.uint8,)
-    if frames.dim() != 4 or frames.dtype not in ok or not frames.is_contiguous():
-        raise ValueError("crop_resize_act: frames must be a contiguous (T,H,W,C) %s tensor" % ("uint8/float32" if resample == "aa" else "uint8 (PIL images are 8-bit)"))
+    t, h, w, c = _frames_arg("crop_resize_act", frames, pil=resample == "pil")
     if resample == "pil" and (flip or float(divisor) != 255.0):
         raise ValueError("crop_resize_act: resample='pil' is to_tensor's / 255 without a flip (crop_resize_pil)")
     if cpad not in (4, 8):
         raise ValueError("crop_resize_act: cpad must be 4 (pixel pairs) or 8")
-    t, h, w, c = frames.shape
     y0, x0, ch, cw = [int(v) for v in box]
     oh, ow = int(out_hw[0]), int(out_hw[1])
     if cpad == 4 and ow % 2:

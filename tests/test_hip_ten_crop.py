@@ -79,6 +79,21 @@ def test_ten_crop_records_with_another_divisor():
     _check_case(CASES[1], "f16", kinds=("u8",), divisor=128.0)
 
 
+def test_ten_crop_records_of_one_channel_frames_equal_those_of_zero_padded_channels():
+    """C = 1: the `c < C` branches. A zero channel resamples to +0, which is what the kernel writes for c >= C: the records of (T,H,W,1) frames have the bits
+    of the records of the 3-channel frames whose channels 1 and 2 are zero; uint8 and float frames (W - cw is odd: two centre column origins)."""
+    from ted_spad_amd import preprocess
+    v1 = (synth_tensor(0, "ten_c1", (20, 50, 70, 1)) * 256).floor().clamp(0, 255)
+    v3 = torch.cat([v1, torch.zeros(20, 50, 70, 2)], dim=3)
+    stem = _stem("f16")
+    for cast in (lambda x: x.to(torch.uint8).cuda(), lambda x: x.cuda()):
+        got = preprocess.ten_crop_records(cast(v1), (40, 57), (32, 48), stem, 1)
+        want = preprocess.ten_crop_records(cast(v3), (40, 57), (32, 48), stem, 1)
+        torch.cuda.synchronize()
+        assert torch.equal(_bits(got), _bits(want))
+        assert bool(_bits(want).any())
+
+
 def test_ten_crop_records_fill_out():
     from ted_spad_amd import preprocess
     t, first, h, w, ch, cw, oh, ow, n_clips = CASES[1]
