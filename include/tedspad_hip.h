@@ -867,6 +867,38 @@ int32_t tedspad_l1_loss_grad_cl(const void *y, int32_t ld, const float *x, void 
 int32_t tedspad_l1_loss_flat(const float *y, const float *x, float *dy, float *ws, float *loss, int64_t numel, int32_t c, int64_t hw, float grad_scale,
                              void *stream);
 
+/* ---- the optimizer tail of a training step: GradScaler's non-finite check and unscale, torch.optim.Adam / AdamW / SGD, GradScaler.update ----
+ * (action_training/train_action.py:79-81 `scaler.scale(loss).backward(); scaler.step(optimizer); scaler.update()`, :251-259 the optimizer choice.)
+ * A whole network is updated by at most three launches whose count and host work do not depend on the number of tensors:
+ *   tedspad_optim_check   reads every gradient of the table once, writes nothing to them, stores 1 to state[0] if any value is not finite (racing writers store
+ *                         the same constant: no atomics). Left out when the step runs without a loss scale.
+ *   tedspad_optim_update  one launch for adam / adamw / sgd. Does nothing at all when state[0] is set. Multiplies each gradient by 1 / *scale (scale NULL: by 1) and
+ *                         applies torch's single-tensor arithmetic in fp32 (no amsgrad, no maximize, dampening 0, no nesterov), t = state[1] + 1:
+ *                           adam   g += wd p (wd != 0); m += (1 - b1)(g - m); v = b2 v + (1 - b2) g g; p -= (lr / (1 - b1^t)) m / (sqrt(v) / sqrt(1 - b2^t) + eps)
+ *                           adamw  p -= lr wd p, then adam with wd = 0
+ *                           sgd    g += wd p; buf = mu buf + g (buf starts as zeros, so the first applied step leaves buf = g); p -= lr buf; mu = 0 keeps no buffer (m NULL)
+ *   tedspad_optim_finish  one tiny launch (a kernel of its own: folded into the update it would need an arrival counter across workgroups), no host synchronisation:
+ *                         out[0] = found_inf as 0 / 1, out[1] = the scale the gradients of this step carried (1 without scale_state); state[1] += !found_inf and the
+ *                         bias corrections of the next step; GradScaler.update() on scale_state when growth_interval > 0 (found_inf: scale *= backoff, tracker = 0;
+ *                         else ++tracker and at growth_interval scale *= growth, tracker = 0), growth_interval <= 0 leaves the scale alone (a static scale); state[0] = 0.
+ * table: nchunks records ON THE DEVICE, each one contiguous run of at most tedspad_optim_chunk_elems() elements of ONE tensor; a workgroup reads its record into
+ * scalar registers. p, m, v 16-byte aligned take 16-byte accesses; g may sit at any 4-byte phase (16-byte loads where it is 16-byte aligned, dwords where not;
+ * the check walks g alone and aligns itself on it: head, 16-byte body, tail). An element's result does not depend on the path that handled it.
+ * state: 8 int32 words on the device {found_inf, t (applied steps), fp32 bits of 1 - b1^(t+1), fp32 bits of sqrt(1 - b2^(t+1)), double b1^(t+1), double b2^(t+1)}
+ * (the caller initialises them; adam / adamw only read words 2-3). scale_state: {fp32 scale, int32 growth tracker}. mode: 0 adam, 1 adamw, 2 sgd. */
+typedef struct tedspad_optim_chunk {
+    float *p;
+    const float *g;
+    float *m, *v;
+    int64_t n, reserved;
+} tedspad_optim_chunk;
+int32_t tedspad_optim_chunk_elems(void);
+int32_t tedspad_optim_check(const tedspad_optim_chunk *table, int32_t nchunks, int32_t *state, void *stream);
+int32_t tedspad_optim_update(const tedspad_optim_chunk *table, int32_t nchunks, int32_t mode, const int32_t *state, const float *scale, float lr, double beta1,
+                             double beta2, float eps, float weight_decay, float momentum, void *stream);
+int32_t tedspad_optim_finish(int32_t *state, float *scale_state, double beta1, double beta2, float growth, float backoff, int32_t growth_interval, float *out,
+                             void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -168,6 +168,10 @@ SYMBOLS = {
     "tedspad_l1_ws_floats": (_I32, []),
     "tedspad_l1_loss_grad_cl": (_I32, [_P, _I32, _P, _P, _P, _P, _P, _I32, _I64, C.c_float, _I32, _P]),
     "tedspad_l1_loss_flat": (_I32, [_P, _P, _P, _P, _P, _I64, _I32, _I64, C.c_float, _P]),
+    "tedspad_optim_chunk_elems": (_I32, []),
+    "tedspad_optim_check": (_I32, [_P, _I32, _P, _P]),
+    "tedspad_optim_update": (_I32, [_P, _I32, _I32, _P, _P, C.c_float, C.c_double, C.c_double, C.c_float, C.c_float, C.c_float, _P]),
+    "tedspad_optim_finish": (_I32, [_P, _P, C.c_double, C.c_double, C.c_float, C.c_float, _I32, _P, _P]),
 }
 
 _lib = None

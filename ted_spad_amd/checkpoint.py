@@ -4,8 +4,9 @@
     save_action_checkpoint(path, epoch, ft, optimizer, loss_scale)         action_training/train_anonymized_action.py:388-414
     save_reconstruction_checkpoint(path, epoch, lr_counter, fa, optimizer) fa_pretraining/train_reconstruction.py:179-196
 
-`epoch` is stored as `epoch + 1`, as the scripts do. The action script stores its `GradScaler` object under 'amp_scaler'; this build has a
-static loss scale and no GradScaler, so the key holds the plain dict {'scale': loss_scale} (a file torch.load reads with weights_only=True).
+`epoch` is stored as `epoch + 1`, as the scripts do. The action script stores its `GradScaler` object under 'amp_scaler'; here the key holds a plain
+dict (a file torch.load reads with weights_only=True): {'scale': loss_scale} for the drivers with a static loss scale, the `state_dict()` of the
+optim.DynamicLossScale (GradScaler.state_dict()'s keys) for ActionTrainStep (`scaler=`).
 """
 from __future__ import annotations
 
@@ -43,10 +44,13 @@ def save_reconstruction_checkpoint(path, epoch, lr_counter, fa, optimizer):
     return states
 
 
-def save_action_checkpoint(path, epoch, ft, optimizer, loss_scale):
+def save_action_checkpoint(path, epoch, ft, optimizer, loss_scale, scaler=None):
+    """scaler: an optim.DynamicLossScale (ActionTrainStep.scaler): 'amp_scaler' then holds its `state_dict()` -- the keys of GradScaler.state_dict(), what
+    `GradScaler.load_state_dict` takes -- and `loss_scale` is not looked at. Without it the file is what it always was. `optimizer` may be a torch.optim
+    optimizer or an optim.FusedOptimizer: both write torch's state_dict layout."""
     states = {
         "epoch": epoch + 1,
-        "amp_scaler": {"scale": float(loss_scale)},
+        "amp_scaler": {"scale": float(loss_scale)} if scaler is None else scaler.state_dict(),
         "ft_model_state_dict": ft.state_dict(),
         "optimizer": optimizer.state_dict(),
     }

@@ -30,13 +30,19 @@ Data parallel: one process per GPU, per-rank BatchNorm statistics (what nn.DataP
 reference). The gradients of the network being updated live in flat buckets (grad_reduce.GradBucketReducer): on
 the LAST backward pass of a step every bucket is all-reduced (RCCL) as soon as the backward sequence has finished its stage,
 overlapped with the backward of the earlier stages; the optimizer then reads the averaged buckets in place.
+
+`ActionTrainStep` and `ActionSchedule` (end of this file) are the two action-training scripts as they run by default: one clip per sample or the triplet
+variant, with or without the frozen anonymizer, the optimizer the script selects and its GradScaler as HIP kernels (optim.py, csrc/optim.hip). The drivers
+above keep torch.optim.
 """
 from __future__ import annotations
 
 from types import SimpleNamespace
 
+import math
 import os
 
+import numpy as np
 import torch
 import torch.distributed as dist
 
@@ -341,6 +347,7 @@ class AnonymizerTrainStep(StepDriver):
             def body(x, lab):
                 pred, feat, tape = self.ft_tr.forward(x, mode, drop_mask=dm, groups=3)
                 P3, F3 = pred.detach().requires_grad_(), feat.detach().requires_grad_()
+                self._pred1 = pred.detach()[:nb]                   # clip 1's logits (ActionTrainStep: training accuracy)
                 losses = self._utility_losses([(P3[k * nb:(k + 1) * nb], F3[k * nb:(k + 1) * nb]) for k in range(3)], lab)
                 self._post(dict(loss_ft=losses[0], loss_ce=losses[1], loss_temporal=losses[2]))
                 losses[0].backward()
@@ -353,6 +360,7 @@ class AnonymizerTrainStep(StepDriver):
             pred, feat, tape = self.ft_tr.forward(c, mode, drop_mask=None if drop_masks is None else drop_masks[k])
             tapes.append(tape)
             leaves.append((pred.detach().requires_grad_(), feat.detach().requires_grad_()))
+        self._pred1 = leaves[0][0].detach()
         losses = self._utility_losses(leaves, labels)
         self._post(dict(loss_ft=losses[0], loss_ce=losses[1], loss_temporal=losses[2]))
         losses[0].backward()
@@ -445,3 +453,188 @@ class AnonymizerTrainStep(StepDriver):
         if self.iteration % 2 == 0:
             return self.step_fa(inputs_video, labels, inputs_vispr)
         return self.step_ft(inputs_video, labels, inputs_vispr=inputs_vispr)
+
+
+# ------------------------------------------------------------------------------------------------------------------------------------------
+# Action training as the scripts run it (action_training/train_action.py, train_anonymized_action.py): optimizer choice, GradScaler, schedule
+# ------------------------------------------------------------------------------------------------------------------------------------------
+
+# action_training/params_action.py:7-48 (params_anonymized_action.py has the same values for every field used here)
+DEFAULT_ACTION_PARAMS = SimpleNamespace(
+    arch="largei3d", num_frames=16, batch_size=16, learning_rate=1e-4, num_epochs=100, loss="ce", temporal_loss=None, temporal_loss_weight=0.1,
+    triplet_loss_margin=1.0, warmup_array=list(np.linspace(0.01, 1, 10) + 1e-9), warmup=10, momentum=0.9, weight_decay=1e-4, lr_patience=2,
+    lr_reduce_factor=2, lr_scheduler="cosine",
+    cosine_lr_array=list(np.linspace(0.01, 1, 5)) + [(math.cos(x) + 1) / 2 for x in np.linspace(0, math.pi / 0.99, 100 - 5)], opt_type="adam")
+
+
+class ActionSchedule:
+    """The learning rate of `train_classifier` (train_action.py:268-326,414), one call per statement group:
+
+        sched = ActionSchedule(params, start_epoch=epoch1)
+        for epoch in sched.epochs():                    # :277
+            lr = sched.lr_for_epoch(epoch)              # :300-318  -> ActionTrainStep.step(..., lr=lr)
+            ... train the epoch ...
+            sched.end_epoch(train_loss)                 # :322-326, and the stop rule of :414
+            if sched.should_stop: break
+
+    As in the script: the branches are tried in the order cosine, warm-up, loss_based / patience_based, and an epoch that takes
+    none of them keeps the rate it had; `loss_based` only ever lowers the rate relative to the start (a loss back above 1 keeps the last rate);
+    `best_score` starts at 0, so no positive loss beats it and the patience counter grows every epoch, warm-up epochs included; the drop fires when
+    the counter EQUALS `lr_patience`; the stop rule is `lr < 1e-12 and epoch > 10` and is never applied under cosine. A restart (`start_epoch > 1`)
+    starts all of this state afresh, as the script does."""
+
+    def __init__(self, params=DEFAULT_ACTION_PARAMS, start_epoch: int = 1):
+        self.params, self.start_epoch = params, int(start_epoch)
+        self.best_score = 0                                            # :269
+        self.train_loss = 1000                                         # :271
+        self.learning_rate = params.learning_rate                      # :272
+        self.orig_learning_rate = self.learning_rate                   # :273
+        self.scheduler_epoch, self.scheduler_step = 0, 1               # :274-275
+        self.epoch = self.start_epoch
+        self.should_stop = False
+
+    def epochs(self):
+        return range(self.start_epoch, self.params.num_epochs + 1)     # :277
+
+    def lr_for_epoch(self, epoch: int) -> float:
+        p = self.params
+        self.epoch = epoch
+        if p.lr_scheduler == "cosine":                                 # :300
+            self.learning_rate = p.cosine_lr_array[epoch - 1] * self.orig_learning_rate
+        elif p.warmup and epoch - 1 < len(p.warmup_array):             # :302
+            self.learning_rate = p.warmup_array[epoch - 1] * self.orig_learning_rate
+        elif p.lr_scheduler == "loss_based":                           # :304
+            if 0.5 <= self.train_loss < 1.0:
+                self.learning_rate = self.orig_learning_rate / 2
+            elif 0.1 <= self.train_loss < 0.5:
+                self.learning_rate = self.orig_learning_rate / 10
+            elif self.train_loss < 0.1:
+                self.learning_rate = self.orig_learning_rate / 20
+        elif p.lr_scheduler == "patience_based":                       # :311
+            if self.scheduler_epoch == p.lr_patience:
+                self.learning_rate = self.orig_learning_rate / (p.lr_reduce_factor ** self.scheduler_step)
+                self.scheduler_epoch = 0
+                self.scheduler_step += 1
+        return self.learning_rate
+
+    def end_epoch(self, train_loss: float) -> bool:
+        """After the epoch's training (:320-326) and at the bottom of the loop (:414). Returns `should_stop`."""
+        self.train_loss = train_loss
+        if train_loss < self.best_score:                               # :322
+            self.best_score = train_loss
+            self.scheduler_epoch = 0
+        else:
+            self.scheduler_epoch += 1
+        self.should_stop = bool(self.params.lr_scheduler != "cosine" and self.learning_rate < 1e-12 and self.epoch > 10)      # :414
+        return self.should_stop
+
+
+class ActionTrainStep(AnonymizerTrainStep):
+    """`train_epoch` of action_training/train_action.py:44-85 (`fa_model=None`: the clips go straight to ft) and train_anonymized_action.py:43-94
+    (a frozen `fa` in front, run under no_grad with the Q2 feed) for `arch='largei3d'`: freeze_bn (I3DTrainer mode 'frozen'), cross-entropy on clip 1's
+    logits, `temporal_loss=None` (one clip per sample, (B,16,3,H,W); the script's default) or 'trip' ((B,48,3,H,W), + w * triplet), the optimizer the
+    script selects (:251-259: adam without weight decay, adamw with `weight_decay`, sgd with `momentum` and `weight_decay`) and its GradScaler -- both on
+    the HIP path (optim.FusedOptimizer, optim.DynamicLossScale: csrc/optim.hip), nothing of torch.optim.
+
+    loss_scale: "dynamic" = GradScaler() (65536, x2 after 2000 clean steps, /2 on an overflow); a float = that static scale (the other drivers'
+    behaviour); None = no scaling and no non-finite check; or a DynamicLossScale.
+
+    Parameters without a gradient are excluded from the step, as torch.optim skips a parameter whose `.grad` is None (no decay, no moment update): the
+    FrozenBN gamma / beta, and with `temporal_loss=None` the whole mlp head (`feat1` never reaches the loss; its BatchNorm1d running statistics still
+    move, the forward runs it).
+
+    The unscale happens inside the update kernel: after a step `.grad` holds the SCALED gradients, and the result's `grad_scale` is the factor they carry."""
+
+    def __init__(self, ft_model, fa_model=None, params=DEFAULT_ACTION_PARAMS, opt_type=None, loss_scale="dynamic", group=None):
+        from .optim import DynamicLossScale, FusedOptimizer
+        p = params
+        if getattr(p, "arch", "largei3d") != "largei3d":
+            raise NotImplementedError("ActionTrainStep: arch %r is not implemented (only 'largei3d')" % p.arch)
+        if p.loss != "ce":
+            raise NotImplementedError("Loss function %s not yet implemented." % p.loss)          # train_action.py:227 ('con' is rejected there too)
+        if p.temporal_loss not in (None, "trip"):
+            raise NotImplementedError("ActionTrainStep: temporal_loss %r is not implemented (None or 'trip')" % (p.temporal_loss,))
+        self.fa, self.ft, self.fb, self.params, self.group = fa_model, ft_model, None, params, group
+        E.apply_env_determinism()
+        self.batch_clips = os.environ.get("TEDSPAD_TRAIN_BATCH_CLIPS", "1") != "0"
+        self.lazy_losses = os.environ.get("TEDSPAD_TRAIN_LAZY_LOSSES", "0") == "1"
+        self._pin, self._pin_used, self._posted = None, 0, []
+        self.ft_tr = I3DTrainer(ft_model)
+        self.ce = CrossEntropyLoss()
+        self.trip = TripletMarginLoss(margin=getattr(p, "triplet_loss_margin", 1.0))             # nn.TripletMarginLoss(), :231
+        self.iteration = 0
+        self.red_ft = GradBucketReducer(self.ft_tr.grad_buckets(), group, all_params=list(ft_model.parameters()))
+        self._frozen_bn_params = [q for n_, q in ft_model.named_parameters()
+                                  if n_.startswith("i3d.") and (".bn" in n_ or n_.startswith("i3d.bn") or ".downsample.1." in n_)]
+        self._excluded = list(self._frozen_bn_params)
+        if p.temporal_loss is None:
+            self._excluded += list(ft_model.mlp.parameters())
+        self.opt_type = opt_type if opt_type is not None else p.opt_type
+        kw = dict(lr=p.learning_rate, exclude=self._excluded)
+        if self.opt_type == "adamw":
+            kw["weight_decay"] = p.weight_decay                                                  # :255
+        elif self.opt_type == "sgd":
+            kw.update(momentum=p.momentum, weight_decay=p.weight_decay)                          # :257
+        self.opt = FusedOptimizer(self.red_ft, self.opt_type, **kw)                              # :253 (adam: lr only)
+        self.opt.set_params_order(ft_model.parameters())
+        self.opt_ft = self.opt
+        if loss_scale == "dynamic":
+            self.scaler = DynamicLossScale()                                                     # :228
+        elif loss_scale is None or isinstance(loss_scale, DynamicLossScale):
+            self.scaler = loss_scale
+        else:
+            self.scaler = DynamicLossScale.static(float(loss_scale))
+        self.loss_scale = None                       # StepDriver's static float is not used here: `_scaled` reads the device
+
+    def _scaled(self, g):
+        if g is None or self.scaler is None:
+            return g
+        return g * self.scaler.scale_tensor(g.device)
+
+    def step(self, inputs, labels, lr=None, drop_masks=None):
+        """inputs: (B,16,3,H,W) (`temporal_loss=None`) or (B,48,3,H,W) ('trip') fp32 in [0,1], as the loader delivers them; labels int64 (B,).
+        lr: this epoch's rate (ActionSchedule.lr_for_epoch; None keeps the last). Returns dict(loss, loss_ce, loss_temporal (None without 'trip') as
+        floats, skipped: DeviceFlag, pred: int64 (B,) device tensor = top-1 of clip 1's logits (:82, nothing is read back), grad_scale: 0-d device
+        tensor = the scale this step's gradients, still in `.grad`, carry)."""
+        self._posted, self._pin_used = [], 0
+        p = self.params
+        trip = p.temporal_loss == "trip"
+        want_t = p.num_frames * (3 if trip else 1)
+        if inputs.dim() != 5 or inputs.shape[1] != want_t:
+            raise ValueError("ActionTrainStep.step: inputs must be (B,%d,3,H,W) for temporal_loss=%r, got %s" % (want_t, p.temporal_loss, tuple(inputs.shape)))
+        self.ft.train()
+        if self.fa is not None:
+            self.fa.eval()
+        TE.ARENA.reset(inputs.device)
+        self.red_ft.prepare(exclude=self._excluded)                   # :45
+        if self.fa is not None:
+            frames, shape = self._feed(inputs)                        # anonymized :47,54-55 (Q2)
+            with torch.no_grad():
+                x = self.fa(frames).reshape(shape)                    # :56-57
+        else:
+            x = inputs.permute(0, 2, 1, 3, 4)                         # :46
+        if trip:
+            clips = torch.split(x, [p.num_frames] * 3, dim=2)         # :55
+            self._three_clips(clips, labels, "frozen", drop_masks)
+        else:
+            dm = None if drop_masks is None else (drop_masks if torch.is_tensor(drop_masks) else drop_masks[0])
+            pred, _, tape = self.ft_tr.forward(x, "frozen", drop_mask=dm)                  # :59-60
+            P = pred.detach().requires_grad_()
+            self._pred1 = pred.detach()
+            loss = self.ce(P, labels)                                 # :68
+            self._post(dict(loss_ft=loss, loss_ce=loss))
+            loss.backward()
+            self.ft_tr.backward(tape, self._scaled(P.grad), None, on_bucket_done=self.red_ft.bucket_ready)
+        self.ft_tr.flush_grads()
+        self.red_ft.finish()
+        found_inf, grad_scale = self.opt.step(lr=lr, scaler=self.scaler)                   # :80-81, on the reduced gradients: all ranks decide alike
+        self.iteration += 1
+        self._check_deterministic()
+        v = self._collect()
+        return dict(phase="action", loss=v["loss_ft"], loss_ce=v["loss_ce"], loss_temporal=v.get("loss_temporal"),
+                    skipped=found_inf != 0 if self.lazy_losses else DeviceFlag(found_inf), pred=self._pred1.argmax(dim=1), grad_scale=grad_scale)
+
+    def step_fa(self, *a, **k):
+        raise NotImplementedError("ActionTrainStep trains ft only")
+
+    step_ft = step_action = step_fa
