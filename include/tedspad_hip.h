@@ -543,7 +543,7 @@ int32_t tedspad_resize_aa_table(int32_t in_size, int32_t out_size, int32_t *tabl
  * uint8 or float (in_is_float) -> value / divisor (255) -> crop [y0,y0+ch) x [x0,x0+cw) -> antialiased bilinear
  * resize to (oh,ow) with the two device tables above (for ch->oh and cw->ow) -> optional horizontal flip (ten-crop)
  * -> fp32 out[t*so_t + c*so_c + y*so_h + x*so_w] (element strides: (T,C,h,w) as the reference returns it, or
- * straight into a (C,T,h,w) clip of the encoder's batch). */
+ * straight into a (C,T,h,w) clip of the encoder's batch). T * oh < 2^31 (one workgroup per frame and output row). */
 int32_t tedspad_frames_crop_resize(const void *frames, int32_t in_is_float, int32_t T, int32_t H, int32_t W, int32_t C,
                                    int32_t y0, int32_t x0, int32_t ch, int32_t cw, int32_t oh, int32_t ow,
                                    const int32_t *ytab, const int32_t *xtab, float divisor, int32_t flip, float *out,

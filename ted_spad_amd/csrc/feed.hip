@@ -644,6 +644,7 @@ extern "C" int32_t tedspad_frames_crop_resize(const void *frames, int32_t in_is_
     ResizeKP p;
     const int32_t rc = aa_args(who, frames, out, ytab, xtab, T, H, W, C, 4, 0, nullptr, false, y0, x0, ch, cw, oh, ow, divisor, flip, &p);
     if (rc != TEDSPAD_OK) return rc;
+    TS_REQUIRE((long)T * oh < (1L << 31), "tedspad_frames_crop_resize: %d frames x %d rows do not fit one launch", T, oh);
     const size_t lds = (size_t)cw * C * sizeof(float);
     TS_REQUIRE(lds <= 64 * 1024, "tedspad_frames_crop_resize: crop width %d x %d channels exceeds the 64 KB LDS row buffer", cw, C);
     p.out = out; p.so_t = so_t; p.so_c = so_c; p.so_h = so_h; p.so_w = so_w;
