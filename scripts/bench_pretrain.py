@@ -15,7 +15,6 @@ import time
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))   # the repository root
-from ted_spad_amd import train_engine as TE
 from ted_spad_amd.model_loaders import load_fa_model
 from ted_spad_amd.pretrain import ReconstructionTrainStep
 from ted_spad_amd.synth import synth_state_dict, synth_tensor
@@ -49,10 +48,8 @@ def timed(fn, steps, warmup):
 
 def pieces_step(step, x):
     """`step.step` with the loss outside the library: fp32 NCHW output, torch's sub / abs / mean and their autograd backward, the fp32 gradient converted back."""
-    step._posted, step._pin_used = [], 0
     step.fa.train()
-    step.opt.zero_grad(set_to_none=True)
-    TE.ARENA.reset(x.device)
+    step._begin(x.device, (step.opt,))
     step.red.prepare(exclude=step._off_path)
     step.loss_scale = step.scale_for(x)
     y, tape = step.fa_tr.forward(x)
@@ -61,11 +58,8 @@ def pieces_step(step, x):
     step._post(dict(loss=loss))
     (loss * step.loss_scale).backward()
     step.fa_tr.backward(tape, y.grad, on_bucket_done=step.red.bucket_ready)
-    step.fa_tr.flush_grads()
-    step.red.finish()
-    skipped = step._opt_step(step.opt, step._unscale(step.fa), step.fa)
-    step.iteration += 1
-    return dict(loss=step._collect()['loss'], skipped=skipped)
+    v, skipped = step._end(step.fa_tr, step.red, step.opt, step.fa)
+    return dict(loss=v['loss'], skipped=skipped)
 
 
 gain = (torch.arange(1, a.batch + 1, device='cuda').float() / a.batch).view(-1, 1, 1, 1)

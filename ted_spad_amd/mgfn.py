@@ -382,17 +382,10 @@ class MGFNTrainStep(StepDriver):
         if int(batch_size) < 1 or not 1 <= int(k) <= 8 or not 0.0 <= float(dropout_rate) < 1.0:
             raise ValueError("MGFNTrainStep: needs batch_size >= 2, 1 <= k <= 8 and 0 <= dropout_rate < 1")
         require_cuda(model.to_tokens.weight, "MGFNTrainStep")
+        super().__init__(loss_scale=1.0, env=False)                   # fp32 throughout: no scale, the floats are always read back
         self.model, self.n, self.k, self.p, self.generator = model, int(batch_size), int(k), float(dropout_rate), generator
-        self.loss_scale, self.lazy_losses = 1.0, False
-        self._pin, self._pin_used, self._posted = None, 0, []
-        self.opt = torch.optim.Adam(model.parameters(), lr=lr, weight_decay=weight_decay)             # main.py:72-73
-        self.iteration = 0
+        self.opt = torch.optim.Adam(model.parameters(), lr=lr, weight_decay=weight_decay)             # main.py:72-73; `set_lr` is :91-93
         self._geo = {}
-
-    def set_lr(self, lr: float):
-        """main.py:91-93: `for param_group in optimizer.param_groups: param_group["lr"] = config.lr[step - 1]`."""
-        for g in self.opt.param_groups:
-            g["lr"] = lr
 
     # ---- shapes ----
     def _geometry(self, nc, T, dev):
@@ -443,7 +436,7 @@ class MGFNTrainStep(StepDriver):
         `score_normal`, `score_abnormal` (batch_size, 1), `scores` (2 batch_size, T, 1), `idx_normal`, `idx_abnormal` (batch_size, k)."""
         model, n, k = self.model, self.n, self.k
         nc, T = self._check(ninput, ainput, nlabel, alabel, masks)
-        self._posted, self._pin_used = [], 0
+        self._begin()                                                                   # (no arena; the gradients are assigned, not accumulated)
         model.train()                                                                   # train.py:81
         dev = model.to_tokens.weight.device
         bounds, seq_off_d, seg_off_d, nseq = self._geometry(nc, T, dev)

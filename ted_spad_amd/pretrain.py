@@ -21,14 +21,11 @@ mathematics, only which values are representable. DESIGN.md "Reconstruction pre-
 """
 from __future__ import annotations
 
-import os
 from types import SimpleNamespace
 
 import numpy as np
 import torch
 
-from . import engine as E
-from . import train_engine as TE
 from .grad_reduce import GradBucketReducer
 from .losses import l1_flat, l1_train
 from .train_nets import UNetPPTrainer
@@ -98,6 +95,8 @@ class ReconstructionSchedule:
 
 
 class ReconstructionTrainStep(StepDriver):
+    check_at_scale_1 = True                     # an automatic scale is 1 for some shapes: the non-finite check runs all the same
+
     def __init__(self, fa_model, learning_rate: float = 1e-3, loss_scale=None, group=None):
         """fa_model: unetpp.UnetPlusPlus (cuda) -- `load_fa_model(arch='unet++')`, train_reconstruction.py:105. learning_rate: parameters.py:12 (the
         script rewrites it every epoch: `set_lr`). loss_scale: None = `auto_loss_scale` of each batch's shape; a number is used as given."""
@@ -105,51 +104,28 @@ class ReconstructionTrainStep(StepDriver):
         if not isinstance(fa_model, UnetPlusPlus):
             raise TypeError("ReconstructionTrainStep trains the unet++ anonymizer (unetpp.UnetPlusPlus, what train_reconstruction.py:105 builds); got %s"
                             % type(fa_model).__name__)
-        self.fa, self.group = fa_model, group
         self.fixed_scale = None if loss_scale is None else float(loss_scale)
-        self.loss_scale = self.fixed_scale if self.fixed_scale is not None else 1.0
-        E.apply_env_determinism()
-        self.lazy_losses = os.environ.get("TEDSPAD_TRAIN_LAZY_LOSSES", "0") == "1"
-        self._pin, self._pin_used, self._posted = None, 0, []         # loss read-back (_post / _collect)
+        super().__init__(self.fixed_scale if self.fixed_scale is not None else 1.0)
+        self.fa, self.group = fa_model, group
         self.fa_tr = UNetPPTrainer(fa_model)
         self._off_path = self.fa_tr.off_path_params()                 # encoder.layer4 (never run): no gradient
-        self.opt = fused_adam(fa_model, learning_rate)                # :123
+        self.opt = fused_adam(fa_model, learning_rate)                # :123; `set_lr` is :28-29
         self.red = GradBucketReducer(self.fa_tr.grad_buckets(), group, all_params=list(fa_model.parameters()))
-        self.iteration = 0
-
-    def set_lr(self, lr: float):
-        """`for param_group in optimizer.param_groups: param_group['lr'] = lr` (train_reconstruction.py:28-29)."""
-        for g in self.opt.param_groups:
-            g["lr"] = lr
 
     def scale_for(self, images) -> float:
         return self.fixed_scale if self.fixed_scale is not None else auto_loss_scale(images.numel(), self.fa.compute_dtype)
 
-    def _unscale(self, module):
-        """As StepDriver's, but the non-finite check also runs when the scale happens to be 1 (an automatic scale is 1 for some shapes)."""
-        grads = [p.grad for p in module.parameters() if p.grad is not None]
-        found_inf = torch.zeros((), device=grads[0].device)
-        torch._amp_foreach_non_finite_check_and_unscale_(grads, found_inf, torch.full((), 1.0 / self.loss_scale, device=grads[0].device))
-        return found_inf
-
     def step(self, images):
         """images (B,3,H,W) fp32 cuda in [0,1], H and W multiples of 16: input and target. Returns dict(loss=float, skipped=DeviceFlag)."""
-        self._posted, self._pin_used = [], 0           # (a step that raised between _post and _collect leaves nothing behind)
         self.fa.train()                                               # :35
-        self.opt.zero_grad(set_to_none=True)                          # :43
-        TE.ARENA.reset(images.device)
+        self._begin(images.device, (self.opt,))                       # :43
         self.red.prepare(exclude=self._off_path)
         self.loss_scale = self.scale_for(images)
         y, tape = self.fa_tr.forward(images, nchw=False)              # :45
         loss, dl, _ = l1_train(y, images, self.loss_scale)            # :46 and the first node of :47
         self._post(dict(loss=loss))                                   # :49
         self.fa_tr.backward(tape, dl=dl, on_bucket_done=self.red.bucket_ready)        # :47
-        self.fa_tr.flush_grads()
-        self.red.finish()
-        skipped = self._opt_step(self.opt, self._unscale(self.fa), self.fa)            # :48
-        self.iteration += 1
-        self._check_deterministic()
-        v = self._collect()
+        v, skipped = self._end(self.fa_tr, self.red, self.opt, self.fa)                # :48
         return dict(loss=v["loss"], skipped=skipped)
 
     def evaluate(self, images):

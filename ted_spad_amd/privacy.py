@@ -14,14 +14,10 @@ computed on `logits > 0.5`, not on probabilities (DESIGN.md "The privacy classif
 """
 from __future__ import annotations
 
-import os
-
 import numpy as np
 import torch
 
-from . import engine as E
 from . import head
-from . import train_engine as TE
 from .train_nets import PredictorTrainer
 from .train_step import StepDriver, fused_adam
 
@@ -30,19 +26,10 @@ class PrivacyTrainStep(StepDriver):
     def __init__(self, fb_model, fa_model=None, learning_rate: float = 1e-3, loss_scale: float = 256.0):
         """fb_model: ResNet50 with an fc (cuda). fa_model: the frozen anonymizer in front (`anon = True`, params_privacy.py:6), or None.
         learning_rate: params_privacy.py:18 (the script rewrites it every epoch: `set_lr`)."""
+        super().__init__(loss_scale)
         self.fb, self.fa = fb_model, fa_model
-        self.loss_scale = float(loss_scale)
-        E.apply_env_determinism()
-        self.lazy_losses = os.environ.get("TEDSPAD_TRAIN_LAZY_LOSSES", "0") == "1"
-        self._pin, self._pin_used, self._posted = None, 0, []         # loss read-back (_post / _collect)
         self.fb_tr = PredictorTrainer(fb_model)
-        self.opt = fused_adam(fb_model, learning_rate)                # train_privacy.py:172
-        self.iteration = 0
-
-    def set_lr(self, lr: float):
-        """`for param_group in optimizer.param_groups: param_group['lr'] = learning_rate` (train_privacy.py:31-32)."""
-        for g in self.opt.param_groups:
-            g["lr"] = lr
+        self.opt = fused_adam(fb_model, learning_rate)                # train_privacy.py:172; `set_lr` is :31-32
 
     def _input(self, images):
         if self.fa is None:
@@ -53,19 +40,13 @@ class PrivacyTrainStep(StepDriver):
 
     def step(self, images, labels):
         """images (B,3,H,W) fp32 cuda, labels (B,N) float (0/1). Returns dict(loss=float, skipped=DeviceFlag)."""
-        self._posted, self._pin_used = [], 0           # (a step that raised between _post and _collect leaves nothing behind)
         self.fb.train()                                               # :39
-        self.opt.zero_grad(set_to_none=True)                          # :42
-        TE.ARENA.reset(images.device)
+        self._begin(images.device, (self.opt,))                       # :42
         x = self._input(images)
         _, loss, tape = self.fb_tr.forward(x, labels, grad_scale=self.loss_scale)     # :49-52: fb forward, fc + BCEWithLogitsLoss fused
         self._post(dict(loss=loss))                                   # :53
         self.fb_tr.backward(tape)                                     # :55
-        self.fb_tr.flush_grads()
-        skipped = self._opt_step(self.opt, self._unscale(self.fb), self.fb)            # :56
-        self.iteration += 1
-        self._check_deterministic()
-        v = self._collect()
+        v, skipped = self._end(self.fb_tr, None, self.opt, self.fb)   # :56
         return dict(loss=v["loss"], skipped=skipped)
 
     def evaluate(self, images, labels):

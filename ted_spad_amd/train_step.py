@@ -124,9 +124,53 @@ def fused_adam(m, lr):
 
 
 class StepDriver:
-    """What the step drivers share: the loss read-back (`_post` / `_collect`), the static loss scale (`_scaled` / `_unscale`), the optimizer step
-    with the non-finite skip (`_opt_step`) and the deterministic-mode check. A subclass sets `loss_scale`, `lazy_losses`, `_pin`, `_pin_used`
-    and `_posted` (AnonymizerTrainStep.__init__, privacy.PrivacyTrainStep.__init__)."""
+    """What every step driver is made of. `__init__` owns the state they share: the determinism hook, `lazy_losses` (TEDSPAD_TRAIN_LAZY_LOSSES, read
+    here and nowhere else; a plain attribute afterwards), the loss read-back (`_pin`, `_pin_used`, `_posted`; `_post` / `_collect`), `iteration` and the
+    static `loss_scale` (`_scaled` / `_unscale`). A step body is
+
+        (mode switches)   self._begin(device, optimizers)   its own prepare / forward / _post / backward   v, skipped = self._end(trainer, reducer, opt, module)
+
+    `_update` is one optimizer tail on its own (a step that updates two networks: `_update` for the first, `_end` for the last); `_apply` is the
+    unscale + optimizer step inside it, with the non-finite skip (`_opt_step`). A driver whose scale does not live in `loss_scale` overrides `_scaled` and
+    `_apply` (ActionTrainStep); one that checks for non-finite gradients even at scale 1 sets `check_at_scale_1`."""
+    check_at_scale_1 = False
+
+    def __init__(self, loss_scale: float = 1.0, env: bool = True):
+        """env=False: neither the determinism hook nor TEDSPAD_TRAIN_LAZY_LOSSES (mgfn.MGFNTrainStep)."""
+        if env:
+            E.apply_env_determinism()
+        self.lazy_losses = env and os.environ.get("TEDSPAD_TRAIN_LAZY_LOSSES", "0") == "1"
+        self.loss_scale = float(loss_scale)
+        self._pin, self._pin_used, self._posted = None, 0, []         # loss read-back (_post / _collect)
+        self.iteration = 0
+
+    def set_lr(self, lr: float):
+        """`for param_group in optimizer.param_groups: param_group['lr'] = lr`, as the scripts do every epoch (the drivers with one `self.opt`)."""
+        for g in self.opt.param_groups:
+            g["lr"] = lr
+
+    def _begin(self, device=None, opts=()):
+        """Start of a step: nothing of an earlier step that raised between `_post` and `_collect` is left behind, the gradients of `opts` are
+        dropped, the activation arena of `device` starts over."""
+        self._posted, self._pin_used = [], 0
+        for opt in opts:
+            opt.zero_grad(set_to_none=True)
+        if device is not None:
+            TE.ARENA.reset(device)
+
+    def _update(self, trainer, reducer, opt, module, **step_args):
+        """One optimizer tail: the trainer's pending gradients, the reducer's last all-reduce (None: no reducer), unscale + step. Returns `skipped`."""
+        trainer.flush_grads()
+        if reducer is not None:
+            reducer.finish()
+        return self._apply(opt, module, **step_args)
+
+    def _end(self, trainer, reducer, opt, module, **step_args):
+        """End of a step: its (last) optimizer tail, the iteration count, the deterministic-mode check. Returns (`_collect()`, skipped)."""
+        skipped = self._update(trainer, reducer, opt, module, **step_args)
+        self.iteration += 1
+        self._check_deterministic()
+        return self._collect(), skipped
 
     def _post(self, losses: dict):
         """Start reading this step's loss values back NOW: they exist once the forward pass and the loss kernels are queued, long before the backward pass behind
@@ -164,15 +208,22 @@ class StepDriver:
         return g if (g is None or self.loss_scale == 1.0) else g * self.loss_scale
 
     def _unscale(self, module):
-        """Divide the loss scale out of `module`'s gradients. Returns the 0-d device flag "some gradient was not finite" (None without a loss scale).
+        """Divide the loss scale out of `module`'s gradients. Returns the 0-d device flag "some gradient was not finite" (None without a loss scale, unless
+        `check_at_scale_1`).
         Called on the ALL-REDUCED gradients: an overflow on any rank makes the sum non-finite on every rank, so all
         ranks take the same step / skip decision (replicas and Adam step counts stay in lock-step)."""
-        if self.loss_scale == 1.0:
+        if self.loss_scale == 1.0 and not self.check_at_scale_1:
             return None
         grads = [p.grad for p in module.parameters() if p.grad is not None]
         found_inf = torch.zeros((), device=grads[0].device)          # 0-d, as torch.amp.GradScaler's (the fused optimizer subtracts it from its 0-d step counters)
         torch._amp_foreach_non_finite_check_and_unscale_(grads, found_inf, torch.full((), 1.0 / self.loss_scale, device=grads[0].device))
         return found_inf
+
+    def _apply(self, opt, module):
+        return self._opt_step(opt, self._unscale(module), module)
+
+    def _skip_flag(self, found_inf):
+        return found_inf != 0 if self.lazy_losses else DeviceFlag(found_inf)
 
     def _opt_step(self, opt, found_inf, module):
         """optimizer.step(), skipped when `found_inf` is set. With a fused optimizer (the default Adam here) the skip is decided ON THE DEVICE, as torch.amp.GradScaler
@@ -188,7 +239,7 @@ class StepDriver:
                     opt.step()
                 finally:
                     del opt.grad_scale, opt.found_inf
-                return found_inf != 0 if self.lazy_losses else DeviceFlag(found_inf)
+                return self._skip_flag(found_inf)
             if float(found_inf) != 0.0:
                 return _flag(True)
             opt.step()
@@ -207,40 +258,84 @@ class StepDriver:
                                "its result is not reproducible (call engine.set_deterministic(True) again to re-arm)" % E.deterministic_giveups())
 
 
-class AnonymizerTrainStep(StepDriver):
-    def __init__(self, fa_model, ft_model, params=DEFAULT_PARAMS, fb_model=None, group=None, loss_scale: float = 256.0):
-        self.fa, self.ft, self.fb, self.params, self.group = fa_model, ft_model, fb_model, params, group
-        self.loss_scale = float(loss_scale)
-        E.apply_env_determinism()
+class ClipUtility:
+    """The utility side the drivers that train ft on an iteration's clips share (AnonymizerTrainStep, ActionTrainStep): ft's trainer, reducer and
+    frozen-BatchNorm parameter list, the Q2 feed, CE + w * triplet, and forward + loss + backward on the three clips. Mixed into a StepDriver
+    (`_post`, `_scaled`)."""
+
+    def _init_clips(self, ft_model, params, group, margin):
+        self.ft, self.params, self.group = ft_model, params, group
         self.batch_clips = os.environ.get("TEDSPAD_TRAIN_BATCH_CLIPS", "1") != "0"   # the three clips of an iteration as one ft batch (0: three passes, A/B)
-        self.batch_views = os.environ.get("TEDSPAD_TRAIN_BATCH_VIEWS", "1") != "0"   # the two VISPR views as one fa / fb batch with per-view statistics (0: two passes)
-        self.lazy_losses = os.environ.get("TEDSPAD_TRAIN_LAZY_LOSSES", "0") == "1"
-        self._pin, self._pin_used, self._posted = None, 0, []         # loss read-back (_post / _collect)
-        from .unetpp import UnetPlusPlus
-        self.fa_tr, self.ft_tr = (UNetPPTrainer if isinstance(fa_model, UnetPlusPlus) else UNetTrainer)(fa_model), I3DTrainer(ft_model)
-        self.fb_tr = FBTrainer(fb_model) if fb_model is not None else None
-        self._fa_off_path = self.fa_tr.off_path_params() if hasattr(self.fa_tr, "off_path_params") else []   # unet++: encoder.layer4 (never run)
-        self.opt_fa = fused_adam(fa_model, params.learning_rate_fa)
-        self.opt_ft = fused_adam(ft_model, params.learning_rate_ft)
-        self.opt_fb = fused_adam(fb_model, params.learning_rate_fb) if fb_model is not None else None
+        self.ft_tr = I3DTrainer(ft_model)
         self.ce = CrossEntropyLoss()
-        self.trip = TripletMarginLoss(margin=params.triplet_loss_margin)
-        self.iteration = 0
-        # gradient buckets in the order each backward sequence finishes them (train_nets.*.grad_buckets)
-        self.red_fa = GradBucketReducer(self.fa_tr.grad_buckets(), group, all_params=list(fa_model.parameters()))
+        self.trip = TripletMarginLoss(margin=margin)
+        # gradient buckets in the order the backward sequence finishes them (train_nets.*.grad_buckets)
         self.red_ft = GradBucketReducer(self.ft_tr.grad_buckets(), group, all_params=list(ft_model.parameters()))
-        self.red_fb = GradBucketReducer(self.fb_tr.grad_buckets(), group, all_params=list(fb_model.parameters())) if self.fb_tr is not None else None
         # freeze_bn (train_anonymized_action.py:39-40): gamma / beta of the trunk's BatchNorm3d layers are buffers there -> no gradient
         self._frozen_bn_params = [p for n_, p in ft_model.named_parameters()
                                   if n_.startswith("i3d.") and (".bn" in n_ or n_.startswith("i3d.bn") or ".downsample.1." in n_)]
 
-    # ---- shared pieces -------------------------------------------------------------------------------------------
     @staticmethod
     def _feed(inputs_video):
         """(B,48,3,H,W) -> the (B*48,3,H,W) pseudo-image batch fa sees (Q2) and the shape to restore."""
         v = inputs_video.permute(0, 2, 1, 3, 4)                       # :57
         b, c, t, h, w = v.shape
         return v.reshape(-1, c, h, w), (b, c, t, h, w)                # :89 (copy: the permuted tensor is not viewable)
+
+    def _utility_losses(self, heads, labels):
+        """heads: [(pred, feat)] x3 as leaf tensors -> (loss_ft, loss_ce, loss_trip)."""
+        p = self.params
+        loss_ce = self.ce(heads[0][0], labels)                        # :107
+        loss_trip = self.trip(heads[0][1], heads[1][1], heads[2][1])  # :115
+        return loss_ce + p.temporal_loss_weight * loss_trip, loss_ce, loss_trip
+
+    def _three_clips(self, clips, labels, mode, drop_masks):
+        """Forward + loss + backward of ft ('train' / 'frozen') on the three clips of an iteration (:169-175 / action :64-84). The reference
+        calls ft_model once per clip; here the three calls are ONE launch sequence over a batch of three GROUPS whose train-mode
+        BatchNorms keep separate batch statistics and update their running statistics group after group (I3DTrainer.forward, groups=3) --
+        whenever every BatchNorm of the trunk sees >= 256 values per channel and group; otherwise three passes as before."""
+        nb = clips[0].shape[0]
+        shape3 = (3 * nb,) + tuple(clips[0].shape[1:])
+        if self.batch_clips and (mode == "frozen" or self.ft_tr.min_group_rows(shape3, 3) >= 256):
+            dm = None if drop_masks is None else torch.cat([m for m in drop_masks], dim=0)
+            pred, feat, tape = self.ft_tr.forward(torch.cat(clips, dim=0), mode, drop_mask=dm, groups=3)
+            P3, F3 = pred.detach().requires_grad_(), feat.detach().requires_grad_()
+            self._pred1 = pred.detach()[:nb]                       # clip 1's logits (ActionTrainStep: training accuracy)
+            losses = self._utility_losses([(P3[k * nb:(k + 1) * nb], F3[k * nb:(k + 1) * nb]) for k in range(3)], labels)
+            self._post(dict(loss_ft=losses[0], loss_ce=losses[1], loss_temporal=losses[2]))
+            losses[0].backward()
+            self.ft_tr.backward(tape, self._scaled(P3.grad), self._scaled(F3.grad), on_bucket_done=self.red_ft.bucket_ready)
+            return losses
+        tapes, leaves = [], []
+        for k, c in enumerate(clips):
+            pred, feat, tape = self.ft_tr.forward(c, mode, drop_mask=None if drop_masks is None else drop_masks[k])
+            tapes.append(tape)
+            leaves.append((pred.detach().requires_grad_(), feat.detach().requires_grad_()))
+        self._pred1 = leaves[0][0].detach()
+        losses = self._utility_losses(leaves, labels)
+        self._post(dict(loss_ft=losses[0], loss_ce=losses[1], loss_temporal=losses[2]))
+        losses[0].backward()
+        for j, (tape, (pl, fl)) in enumerate(zip(tapes, leaves)):     # the third clip's pass finishes every bucket -> all-reduce under it
+            self.ft_tr.backward(tape, self._scaled(pl.grad), self._scaled(fl.grad),
+                                on_bucket_done=self.red_ft.bucket_ready if j == len(tapes) - 1 else None)
+        return losses
+
+
+class AnonymizerTrainStep(ClipUtility, StepDriver):
+    def __init__(self, fa_model, ft_model, params=DEFAULT_PARAMS, fb_model=None, group=None, loss_scale: float = 256.0):
+        StepDriver.__init__(self, loss_scale)
+        self.fa, self.fb = fa_model, fb_model
+        self.batch_views = os.environ.get("TEDSPAD_TRAIN_BATCH_VIEWS", "1") != "0"   # the two VISPR views as one fa / fb batch with per-view statistics (0: two passes)
+        from .unetpp import UnetPlusPlus
+        self.fa_tr = (UNetPPTrainer if isinstance(fa_model, UnetPlusPlus) else UNetTrainer)(fa_model)
+        self._init_clips(ft_model, params, group, params.triplet_loss_margin)
+        self.fb_tr = FBTrainer(fb_model) if fb_model is not None else None
+        self._fa_off_path = self.fa_tr.off_path_params() if hasattr(self.fa_tr, "off_path_params") else []   # unet++: encoder.layer4 (never run)
+        self.opt_fa = fused_adam(fa_model, params.learning_rate_fa)
+        self.opt_ft = fused_adam(ft_model, params.learning_rate_ft)
+        self.opt_fb = fused_adam(fb_model, params.learning_rate_fb) if fb_model is not None else None
+        self.red_fa = GradBucketReducer(self.fa_tr.grad_buckets(), group, all_params=list(fa_model.parameters()))
+        self.red_fb = GradBucketReducer(self.fb_tr.grad_buckets(), group, all_params=list(fb_model.parameters())) if self.fb_tr is not None else None
 
     def _views_batchable(self, views) -> bool:
         """The two VISPR views can run as one batch with per-view BatchNorm statistics: same shape, and every BatchNorm of fa (down to H/16) and fb (down to
@@ -249,13 +344,6 @@ class AnonymizerTrainStep(StepDriver):
             return False
         nb, _, h, w = views[0].shape
         return nb * (h // 32) * (w // 32) >= 256 and h % 32 == 0 and w % 32 == 0
-
-    def _utility_losses(self, heads, labels):
-        """heads: [(pred, feat)] x3 as leaf tensors -> (loss_ft, loss_ce, loss_trip)."""
-        p = self.params
-        loss_ce = self.ce(heads[0][0], labels)                        # :107
-        loss_trip = self.trip(heads[0][1], heads[1][1], heads[2][1])  # :115
-        return loss_ce + p.temporal_loss_weight * loss_trip, loss_ce, loss_trip
 
     def _opts(self):
         return [o for o in (self.opt_fa, self.opt_fb, self.opt_ft) if o is not None]
@@ -270,15 +358,12 @@ class AnonymizerTrainStep(StepDriver):
     # ---- phase 1 --------------------------------------------------------------------------------------------------
     def step_fa(self, inputs_video, labels, inputs_vispr=None):
         """Update fa (phase 1). Returns a dict of python floats (read back as soon as the losses exist, `_post`) + `skipped`, a `DeviceFlag`."""
-        self._posted, self._pin_used = [], 0           # (a step that raised between _post and _collect leaves nothing behind)
         p = self.params
         views = self._views(inputs_vispr)
         self.fa.train(); self.ft.eval()
         if self.fb is not None:
             self.fb.eval()
-        for opt in self._opts():
-            opt.zero_grad(set_to_none=True)
-        TE.ARENA.reset(inputs_video.device)
+        self._begin(inputs_video.device, self._opts())
         self.red_fa.prepare(exclude=self._fa_off_path)                # fa's gradients: zeroed views into the buckets
         fb_ctx, loss_fb = [], None
         if views is not None and self._views_batchable(views):        # :80-84 as ONE batch: fa's BatchNorms keep the statistics of each view (groups = 2), fb is frozen
@@ -325,62 +410,18 @@ class AnonymizerTrainStep(StepDriver):
             for k, (tape, (pl, fl)) in enumerate(zip(tapes, leaves)):
                 self.ft_tr.backward(tape, self._scaled(pl.grad), self._scaled(fl.grad), dx_out=danon[:, :, k * p.num_frames:(k + 1) * p.num_frames])
         self.fa_tr.backward(tape_fa, danon.reshape(anon_flat.shape), on_bucket_done=self.red_fa.bucket_ready)   # fa's last backward pass of the step
-        self.fa_tr.flush_grads()
-        self.red_fa.finish()
-        skipped = self._opt_step(self.opt_fa, self._unscale(self.fa), self.fa)     # :123
-        self.iteration += 1
-        self._check_deterministic()
-        v = self._collect()
+        v, skipped = self._end(self.fa_tr, self.red_fa, self.opt_fa, self.fa)     # :123
         return dict(phase=1, loss_fa=v["loss_fa"], loss_ft=v["loss_ft"], loss_ce=v["loss_ce"], loss_temporal=v["loss_temporal"], loss_fb=v.get("loss_fb"), skipped=skipped)
-
-    def _three_clips(self, clips, labels, mode, drop_masks):
-        """Forward + loss + backward of ft ('train' / 'frozen') on the three clips of an iteration (:169-175 / action :64-84). The reference
-        calls ft_model once per clip; here the three calls are ONE launch sequence over a batch of three GROUPS whose train-mode
-        BatchNorms keep separate batch statistics and update their running statistics group after group (I3DTrainer.forward, groups=3) --
-        whenever every BatchNorm of the trunk sees >= 256 values per channel and group; otherwise three passes as before."""
-        nb = clips[0].shape[0]
-        shape3 = (3 * nb,) + tuple(clips[0].shape[1:])
-        if self.batch_clips and (mode == "frozen" or self.ft_tr.min_group_rows(shape3, 3) >= 256):
-            dm = None if drop_masks is None else torch.cat([m for m in drop_masks], dim=0)
-            x3 = torch.cat(clips, dim=0)
-
-            def body(x, lab):
-                pred, feat, tape = self.ft_tr.forward(x, mode, drop_mask=dm, groups=3)
-                P3, F3 = pred.detach().requires_grad_(), feat.detach().requires_grad_()
-                self._pred1 = pred.detach()[:nb]                   # clip 1's logits (ActionTrainStep: training accuracy)
-                losses = self._utility_losses([(P3[k * nb:(k + 1) * nb], F3[k * nb:(k + 1) * nb]) for k in range(3)], lab)
-                self._post(dict(loss_ft=losses[0], loss_ce=losses[1], loss_temporal=losses[2]))
-                losses[0].backward()
-                self.ft_tr.backward(tape, self._scaled(P3.grad), self._scaled(F3.grad), on_bucket_done=self.red_ft.bucket_ready)
-                return losses
-
-            return body(x3, labels)
-        tapes, leaves = [], []
-        for k, c in enumerate(clips):
-            pred, feat, tape = self.ft_tr.forward(c, mode, drop_mask=None if drop_masks is None else drop_masks[k])
-            tapes.append(tape)
-            leaves.append((pred.detach().requires_grad_(), feat.detach().requires_grad_()))
-        self._pred1 = leaves[0][0].detach()
-        losses = self._utility_losses(leaves, labels)
-        self._post(dict(loss_ft=losses[0], loss_ce=losses[1], loss_temporal=losses[2]))
-        losses[0].backward()
-        for j, (tape, (pl, fl)) in enumerate(zip(tapes, leaves)):     # the third clip's pass finishes every bucket -> all-reduce under it
-            self.ft_tr.backward(tape, self._scaled(pl.grad), self._scaled(fl.grad),
-                                on_bucket_done=self.red_ft.bucket_ready if j == len(tapes) - 1 else None)
-        return losses
 
     # ---- phase 2 --------------------------------------------------------------------------------------------------
     def step_ft(self, inputs_video, labels, drop_masks=None, inputs_vispr=None):
         """Update ft and fb (phase 2)."""
-        self._posted, self._pin_used = [], 0           # (a step that raised between _post and _collect leaves nothing behind)
         p = self.params
         views = self._views(inputs_vispr)
         self.fa.eval(); self.ft.train()
         if self.fb is not None:
             self.fb.train()
-        for opt in self._opts():
-            opt.zero_grad(set_to_none=True)
-        TE.ARENA.reset(inputs_video.device)
+        self._begin(inputs_video.device, self._opts())
         self.red_ft.prepare()
         if self.red_fb is not None:
             self.red_fb.prepare()
@@ -410,17 +451,10 @@ class AnonymizerTrainStep(StepDriver):
             loss_fb.backward()
             for j, (tape_b, z) in enumerate(ctx):
                 self.fb_tr.backward(tape_b, self._scaled(z.grad), on_bucket_done=self.red_fb.bucket_ready if j == len(ctx) - 1 else None)
-            self.fb_tr.flush_grads()
-            self.red_fb.finish()
-            self._opt_step(self.opt_fb, self._unscale(self.fb), self.fb)
+            self._update(self.fb_tr, self.red_fb, self.opt_fb, self.fb)
         clips = torch.split(anon, [p.num_frames] * 3, dim=2)
-        loss_ft, loss_ce, loss_trip = self._three_clips(clips, labels, "train", drop_masks)             # :169-175,191
-        self.ft_tr.flush_grads()
-        self.red_ft.finish()
-        skipped = self._opt_step(self.opt_ft, self._unscale(self.ft), self.ft)     # :193
-        self.iteration += 1
-        self._check_deterministic()
-        v = self._collect()
+        self._three_clips(clips, labels, "train", drop_masks)         # :169-175,191
+        v, skipped = self._end(self.ft_tr, self.red_ft, self.opt_ft, self.ft)     # :193
         return dict(phase=2, loss_ft=v["loss_ft"], loss_ce=v["loss_ce"], loss_temporal=v["loss_temporal"], loss_fb=v.get("loss_fb"), skipped=skipped)
 
     def step_action(self, inputs_video, labels, drop_masks=None):
@@ -429,23 +463,16 @@ class AnonymizerTrainStep(StepDriver):
         BatchNorm3d layers frozen (`freeze_bn`, :39-40: running statistics, gamma / beta are buffers and get no gradient;
         dropout and the mlp head follow the train flag), loss = CE(pred of clip 1) + w * triplet(feat1, feat2, feat3)
         (:64-84), then the optimizer step on ft (:86-88; the GradScaler is the static `loss_scale` here)."""
-        self._posted, self._pin_used = [], 0           # (a step that raised between _post and _collect leaves nothing behind)
         p = self.params
         self.fa.eval(); self.ft.train()
-        self.opt_ft.zero_grad(set_to_none=True)                       # :46
-        TE.ARENA.reset(inputs_video.device)
+        self._begin(inputs_video.device, (self.opt_ft,))              # :46
         self.red_ft.prepare(exclude=self._frozen_bn_params)
         frames, shape = self._feed(inputs_video)                      # :47,54-55 (Q2)
         with torch.no_grad():
             anon = self.fa(frames).reshape(shape)                     # :56-57
         clips = torch.split(anon, [p.num_frames] * 3, dim=2)          # :62
-        loss, loss_ce, loss_trip = self._three_clips(clips, labels, "frozen", drop_masks)
-        self.ft_tr.flush_grads()
-        self.red_ft.finish()
-        skipped = self._opt_step(self.opt_ft, self._unscale(self.ft), self.ft)     # :87
-        self.iteration += 1
-        self._check_deterministic()
-        v = self._collect()
+        self._three_clips(clips, labels, "frozen", drop_masks)
+        v, skipped = self._end(self.ft_tr, self.red_ft, self.opt_ft, self.ft)     # :87
         return dict(phase="action", loss=v["loss_ft"], loss_ce=v["loss_ce"], loss_temporal=v["loss_temporal"], skipped=skipped)
 
     def step(self, inputs_video, labels, inputs_vispr=None):
@@ -529,7 +556,7 @@ class ActionSchedule:
         return self.should_stop
 
 
-class ActionTrainStep(AnonymizerTrainStep):
+class ActionTrainStep(ClipUtility, StepDriver):
     """`train_epoch` of action_training/train_action.py:44-85 (`fa_model=None`: the clips go straight to ft) and train_anonymized_action.py:43-94
     (a frozen `fa` in front, run under no_grad with the Q2 feed) for `arch='largei3d'`: freeze_bn (I3DTrainer mode 'frozen'), cross-entropy on clip 1's
     logits, `temporal_loss=None` (one clip per sample, (B,16,3,H,W); the script's default) or 'trip' ((B,48,3,H,W), + w * triplet), the optimizer the
@@ -554,18 +581,9 @@ class ActionTrainStep(AnonymizerTrainStep):
             raise NotImplementedError("Loss function %s not yet implemented." % p.loss)          # train_action.py:227 ('con' is rejected there too)
         if p.temporal_loss not in (None, "trip"):
             raise NotImplementedError("ActionTrainStep: temporal_loss %r is not implemented (None or 'trip')" % (p.temporal_loss,))
-        self.fa, self.ft, self.fb, self.params, self.group = fa_model, ft_model, None, params, group
-        E.apply_env_determinism()
-        self.batch_clips = os.environ.get("TEDSPAD_TRAIN_BATCH_CLIPS", "1") != "0"
-        self.lazy_losses = os.environ.get("TEDSPAD_TRAIN_LAZY_LOSSES", "0") == "1"
-        self._pin, self._pin_used, self._posted = None, 0, []
-        self.ft_tr = I3DTrainer(ft_model)
-        self.ce = CrossEntropyLoss()
-        self.trip = TripletMarginLoss(margin=getattr(p, "triplet_loss_margin", 1.0))             # nn.TripletMarginLoss(), :231
-        self.iteration = 0
-        self.red_ft = GradBucketReducer(self.ft_tr.grad_buckets(), group, all_params=list(ft_model.parameters()))
-        self._frozen_bn_params = [q for n_, q in ft_model.named_parameters()
-                                  if n_.startswith("i3d.") and (".bn" in n_ or n_.startswith("i3d.bn") or ".downsample.1." in n_)]
+        StepDriver.__init__(self)                    # the static `loss_scale` stays 1 and unused: the scale lives on the device (`_scaled`, `_apply`)
+        self.fa = fa_model
+        self._init_clips(ft_model, params, group, getattr(p, "triplet_loss_margin", 1.0))        # nn.TripletMarginLoss(), :231
         self._excluded = list(self._frozen_bn_params)
         if p.temporal_loss is None:
             self._excluded += list(ft_model.mlp.parameters())
@@ -584,19 +602,23 @@ class ActionTrainStep(AnonymizerTrainStep):
             self.scaler = loss_scale
         else:
             self.scaler = DynamicLossScale.static(float(loss_scale))
-        self.loss_scale = None                       # StepDriver's static float is not used here: `_scaled` reads the device
 
     def _scaled(self, g):
+        """The scale is the scaler's 0-d device tensor, not StepDriver's static float."""
         if g is None or self.scaler is None:
             return g
         return g * self.scaler.scale_tensor(g.device)
+
+    def _apply(self, opt, module, lr=None):
+        """The update kernel checks, unscales and steps (and moves a dynamic scale) on the reduced gradients: all ranks decide alike (:80-81)."""
+        found_inf, self._grad_scale = opt.step(lr=lr, scaler=self.scaler)
+        return self._skip_flag(found_inf)
 
     def step(self, inputs, labels, lr=None, drop_masks=None):
         """inputs: (B,16,3,H,W) (`temporal_loss=None`) or (B,48,3,H,W) ('trip') fp32 in [0,1], as the loader delivers them; labels int64 (B,).
         lr: this epoch's rate (ActionSchedule.lr_for_epoch; None keeps the last). Returns dict(loss, loss_ce, loss_temporal (None without 'trip') as
         floats, skipped: DeviceFlag, pred: int64 (B,) device tensor = top-1 of clip 1's logits (:82, nothing is read back), grad_scale: 0-d device
         tensor = the scale this step's gradients, still in `.grad`, carry)."""
-        self._posted, self._pin_used = [], 0
         p = self.params
         trip = p.temporal_loss == "trip"
         want_t = p.num_frames * (3 if trip else 1)
@@ -605,7 +627,7 @@ class ActionTrainStep(AnonymizerTrainStep):
         self.ft.train()
         if self.fa is not None:
             self.fa.eval()
-        TE.ARENA.reset(inputs.device)
+        self._begin(inputs.device)
         self.red_ft.prepare(exclude=self._excluded)                   # :45
         if self.fa is not None:
             frames, shape = self._feed(inputs)                        # anonymized :47,54-55 (Q2)
@@ -625,16 +647,6 @@ class ActionTrainStep(AnonymizerTrainStep):
             self._post(dict(loss_ft=loss, loss_ce=loss))
             loss.backward()
             self.ft_tr.backward(tape, self._scaled(P.grad), None, on_bucket_done=self.red_ft.bucket_ready)
-        self.ft_tr.flush_grads()
-        self.red_ft.finish()
-        found_inf, grad_scale = self.opt.step(lr=lr, scaler=self.scaler)                   # :80-81, on the reduced gradients: all ranks decide alike
-        self.iteration += 1
-        self._check_deterministic()
-        v = self._collect()
+        v, skipped = self._end(self.ft_tr, self.red_ft, self.opt, self.ft, lr=lr)
         return dict(phase="action", loss=v["loss_ft"], loss_ce=v["loss_ce"], loss_temporal=v.get("loss_temporal"),
-                    skipped=found_inf != 0 if self.lazy_losses else DeviceFlag(found_inf), pred=self._pred1.argmax(dim=1), grad_scale=grad_scale)
-
-    def step_fa(self, *a, **k):
-        raise NotImplementedError("ActionTrainStep trains ft only")
-
-    step_ft = step_action = step_fa
+                    skipped=skipped, pred=self._pred1.argmax(dim=1), grad_scale=self._grad_scale)

@@ -30,10 +30,10 @@ def _x():
 
 def _fused_backward(fa, x, scale):
     """forward(nchw=False) -> kernel -> backward(dl=) -> flush. Returns (loss 0-d, yy fp32 NCHW)."""
-    from ted_spad_amd import train_engine as TE
     from ted_spad_amd.losses import l1_train
     from ted_spad_amd.train_nets import UNetPPTrainer
-    TE.ARENA.reset(x.device)
+    from ted_spad_amd.train_step import StepDriver
+    StepDriver()._begin(x.device)
     tr = UNetPPTrainer(fa.train())
     y, tape = tr.forward(x, nchw=False)
     assert y.dims == (SHAPE[0], 1, SHAPE[2], SHAPE[3]) and y.c == 8
@@ -68,14 +68,14 @@ def device_run():
 def test_fused_path_is_bit_equal_to_the_fp32_ended_path(deterministic):
     """The main correctness statement, no tolerance: forward(nchw=False) -> tedspad_l1_loss_grad_cl -> backward(dl=) gives every parameter the bits of
     forward(x) -> sign(yy - x) * g in fp32 on the device -> backward(tape, dy) (deterministic mode, same weights)."""
-    from ted_spad_amd import train_engine as TE
     from ted_spad_amd.train_nets import UNetPPTrainer
+    from ted_spad_amd.train_step import StepDriver
     x = _x().cuda()
     scale = 256.0
     fa_a, _ = _fa()
     loss, yy_a = _fused_backward(fa_a, x, scale)
     fa_b, _ = _fa()
-    TE.ARENA.reset(x.device)
+    StepDriver()._begin(x.device)
     tr = UNetPPTrainer(fa_b.train())
     yy, tape = tr.forward(x)
     assert torch.equal(yy, yy_a)
