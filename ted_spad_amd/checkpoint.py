@@ -15,17 +15,16 @@ import torch
 
 def save_anonymizer_checkpoint(path, epoch, fa, fb, ft, optimizers=None):
     """optimizers: None (`model_temp.pth` / best-accuracy files, :519-536) or (optimizer_fa, optimizer_fb, optimizer_ft) (every third
-    epoch, :541-550)."""
-    states = {
-        "epoch": epoch + 1,
-        "fa_model_state_dict": fa.state_dict(),
-        "fb_model_state_dict": fb.state_dict(),
-        "ft_model_state_dict": ft.state_dict(),
-    }
+    epoch, :541-550). fb None (AnonymizerTrainStep without a privacy branch, whose `opt_fb` is None too): the file has no fb keys."""
+    states = {"epoch": epoch + 1, "fa_model_state_dict": fa.state_dict()}
+    if fb is not None:
+        states["fb_model_state_dict"] = fb.state_dict()
+    states["ft_model_state_dict"] = ft.state_dict()
     if optimizers is not None:
         opt_fa, opt_fb, opt_ft = optimizers
         states["optimizer_fa"] = opt_fa.state_dict()
-        states["optimizer_fb"] = opt_fb.state_dict()
+        if opt_fb is not None:
+            states["optimizer_fb"] = opt_fb.state_dict()
         states["optimizer_ft"] = opt_ft.state_dict()
     torch.save(states, path)
     return states

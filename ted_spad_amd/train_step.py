@@ -145,9 +145,11 @@ class StepDriver:
         self.iteration = 0
 
     def set_lr(self, lr: float):
-        """`for param_group in optimizer.param_groups: param_group['lr'] = lr`, as the scripts do every epoch (the drivers with one `self.opt`)."""
+        """`for param_group in optimizer.param_groups: param_group['lr'] = lr`, as the scripts do every epoch (the drivers with one `self.opt`). Stored as a
+        Python float: the schedules' warm-up arrays are numpy's, and a numpy scalar in `optimizer.state_dict()` makes a checkpoint that `torch.load` (weights
+        only, what model_loaders uses) refuses to read."""
         for g in self.opt.param_groups:
-            g["lr"] = lr
+            g["lr"] = float(lr)
 
     def _begin(self, device=None, opts=()):
         """Start of a step: nothing of an earlier step that raised between `_post` and `_collect` is left behind, the gradients of `opts` are
