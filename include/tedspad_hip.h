@@ -899,6 +899,17 @@ int32_t tedspad_optim_update(const tedspad_optim_chunk *table, int32_t nchunks, 
 int32_t tedspad_optim_finish(int32_t *state, float *scale_state, double beta1, double beta2, float growth, float backoff, int32_t growth_interval, float *out,
                              void *stream);
 
+/* ---- the attention core of I3Res50's NonLocalBlock, inference (csrc/nonlocal.hip) ----
+ * Replaces large_i3d.py:112-119 (`view` x 3, `bmm(theta^T, phi)`, `* dim_inner**-.5`, `softmax(dim=-1)`, `bmm(g, p^T)`, `view`) with one launch
+ * that never writes the q x k score matrix. Channels-last 16-bit rows: theta (n, q, d) with row stride ld_theta, phi and g (n, k, d) with their
+ * own row strides (two channel slices of one wider buffer: pass each slice's first channel and the buffer's row stride), out (n, q, d):
+ *   out[b, i, :] = sum_j softmax_j(scale * theta[b, i, :] . phi[b, j, :]) * g[b, j, :]
+ * fp32 logits and accumulation, the running maximum subtracted (online softmax over key tiles); the probabilities are rounded to the storage type
+ * for the second product, the row sum is taken of the unrounded ones. q, k >= 1 are arbitrary; every result depends on its own batch item alone
+ * (bit-identical in any batch). d must be 256 or 512 (anything else: TEDSPAD_EINVAL); ld % 8 == 0, 16-byte aligned pointers, out aliases no input. */
+int32_t tedspad_nl_attention_fwd(const void *theta, int32_t ld_theta, const void *phi, int32_t ld_phi, const void *g, int32_t ld_g, void *out, int32_t ld_out,
+                                 int32_t n, int32_t q, int32_t k, int32_t d, float scale, int32_t dtype, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

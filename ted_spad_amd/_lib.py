@@ -172,6 +172,7 @@ SYMBOLS = {
     "tedspad_optim_check": (_I32, [_P, _I32, _P, _P]),
     "tedspad_optim_update": (_I32, [_P, _I32, _I32, _P, _P, C.c_float, C.c_double, C.c_double, C.c_float, C.c_float, C.c_float, _P]),
     "tedspad_optim_finish": (_I32, [_P, _P, C.c_double, C.c_double, C.c_float, C.c_float, _I32, _P, _P]),
+    "tedspad_nl_attention_fwd": (_I32, [_P, _I32, _P, _I32, _P, _I32, _P, _I32, _I32, _I32, _I32, _I32, C.c_float, _I32, _P]),
 }
 
 _lib = None

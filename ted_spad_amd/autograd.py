@@ -176,7 +176,9 @@ class _I3DFn(torch.autograd.Function):
 
 def wrapper_forward(module, x, drop_mask=None):
     """wrapper_i3d.forward with a tape: returns (pred, feat) as autograd-tracked tensors."""
+    from .i3res50 import refuse_nonlocal_training
     from .train_nets import I3DTrainer
+    refuse_nonlocal_training(module, "wrapper_i3d with gradients")
     tr = _trainer(module, I3DTrainer)
     if module.training:
         mode = "frozen" if getattr(module, "frozen_bn", False) else "train"
@@ -272,5 +274,7 @@ def freeze_bn(model):
     target = model if hasattr(model, "i3d") else None
     if target is None:
         raise NotImplementedError("freeze_bn: expected the wrapper_i3d that load_ft_model('largei3d') returns")
+    from .i3res50 import refuse_nonlocal_training
+    refuse_nonlocal_training(model, "freeze_bn")
     target.frozen_bn = True
     return model

@@ -1006,6 +1006,28 @@ def maxpool(x: Act, k, s, pads=(0, 0, 0), pads_back=None, pad_zero=False, out: O
     return (out, idx) if return_idx else out
 
 
+def nl_attention(theta: Act, phi: Act, g: Act, scale: float, out: Optional[Act] = None) -> Act:
+    """out[b, i, :] = sum_j softmax_j(scale * theta[b, i, :] . phi[b, j, :]) g[b, j, :] over the pixels of a batch item (large_i3d.py:112-119), one launch of
+    tedspad_nl_attention_fwd: the score matrix is never written. theta (n, t, h, w, d) are the queries; phi and g (n, t, h', w', d) the keys and values, each
+    an Act with its own row stride and channel offset (two slices of one buffer). d: 256 or 512 -- any other width is the library's error, never a torch path."""
+    n, t, h, w = theta.dims
+    assert phi.dims == g.dims and phi.dims[0] == n and theta.c == phi.c == g.c, "nl_attention: theta %s x %d, phi %s x %d, g %s x %d" % (
+        theta.dims, theta.c, phi.dims, phi.c, g.dims, g.c)
+    assert theta.buf.dtype == phi.buf.dtype == g.buf.dtype
+    if out is None:
+        out = Act.empty(n, t, h, w, theta.c, theta.buf.dtype, theta.buf.device)
+    assert out.dims == theta.dims and out.c == theta.c and out.buf.dtype == theta.buf.dtype
+    q, k = t * h * w, phi.dims[1] * phi.dims[2] * phi.dims[3]
+    code = _lib.F16 if theta.buf.dtype == torch.float16 else _lib.BF16
+    nc = batch_chunk(n, [q * max(theta.ld, out.ld), k * max(phi.ld, g.ld)], MAX_ELEMS)
+    for n0 in range(0, n, nc):
+        n1 = min(n, n0 + nc)
+        ts, ps, gs, os_ = (Act(a.buf[n0:n1], a.c, a.coff) for a in (theta, phi, g, out))
+        check(_lib.lib().tedspad_nl_attention_fwd(ts.ptr, ts.ld, ps.ptr, ps.ld, gs.ptr, gs.ld, os_.ptr, os_.ld, n1 - n0, q, k, theta.c, C.c_float(scale), code,
+                                                  _stream_ptr()), "tedspad_nl_attention_fwd")
+    return out
+
+
 def global_avgpool(x: Act) -> torch.Tensor:
     """(n,t,h,w,c) -> fp32 (n, c): mean over all pixels."""
     n, t, h, w = x.dims

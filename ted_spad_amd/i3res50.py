@@ -20,11 +20,59 @@ from .params import BNParams, ConvParams, LinearParams, params_signature
 LAYER_PLAN = ((64, 3, 1, (1, 1, 1)), (128, 4, 2, (1, 0, 1, 0)), (256, 6, 2, (1, 0, 1, 0, 1, 0)), (512, 3, 2, (0, 1, 0)))
 
 
+class NonLocalBlock(nn.Module):
+    """Parameter layout of large_i3d.py:86-100: theta / phi / g (dim_in -> dim_inner) and out (dim_inner -> dim_out) are 1x1x1 convolutions WITH bias,
+    bn a BatchNorm3d(dim_out); the max-pool in front of phi and g has no parameters. Inference only: `nonlocal_forward` is its launch sequence."""
+
+    def __init__(self, dim_in, dim_out, dim_inner):
+        super().__init__()
+        self.dim_in, self.dim_inner, self.dim_out = dim_in, dim_inner, dim_out
+        self.theta = ConvParams(dim_in, dim_inner, (1, 1, 1), bias=True, init="kaiming_fan_out")
+        self.phi = ConvParams(dim_in, dim_inner, (1, 1, 1), bias=True, init="kaiming_fan_out")
+        self.g = ConvParams(dim_in, dim_inner, (1, 1, 1), bias=True, init="kaiming_fan_out")
+        self.out = ConvParams(dim_inner, dim_out, (1, 1, 1), bias=True, init="kaiming_fan_out")
+        self.bn = BNParams(dim_out)
+
+
+def has_nonlocal(model) -> bool:
+    """True if `model` (an I3Res50, or a wrapper that holds one as `.i3d`) was built with use_nl=True."""
+    return any(isinstance(m, NonLocalBlock) for m in model.modules())
+
+
+def refuse_nonlocal_training(model, who: str) -> None:
+    """The non-local blocks run in eval() only: every training entry point calls this where it is constructed."""
+    if model is not None and has_nonlocal(model):
+        raise NotImplementedError("%s: this network has non-local blocks (use_nl=True) and their backward is not built -- inference only "
+                                  "(extract_features / forward in eval()); train a use_nl=False network" % who)
+
+
+def pack_nonlocal(P: dict, p: str, nl: NonLocalBlock, dtype, device) -> None:
+    """The three weight images of a non-local block into the packed dict `P` under prefix `p`: everything but the attention core runs on the conv kernel."""
+    P[p + "theta"] = E.PackedConv(nl.theta.weight, None, nl.theta.bias, dtype=dtype, device=device)             # scale 1, shift = bias
+    # phi and g read the same pooled tensor: ONE GEMM with cout = 2 * dim_inner; the attention kernel takes the two halves as slices of its output
+    P[p + "phi_g"] = E.PackedConv(torch.cat([nl.phi.weight.detach(), nl.g.weight.detach()]), None, torch.cat([nl.phi.bias.detach(), nl.g.bias.detach()]),
+                                  dtype=dtype, device=device)
+    s, b = E.fold_bn(nl.bn.weight, nl.bn.bias, nl.bn.running_mean, nl.bn.running_var, nl.bn.eps, conv_bias=nl.out.bias)
+    P[p + "out"] = E.PackedConv(nl.out.weight, s, b, dtype=dtype, device=device)                                # out + bn as one scale / shift
+
+
+def nonlocal_forward(P: dict, p: str, nl: NonLocalBlock, a: E.Act) -> E.Act:
+    """NonLocalBlock.forward (large_i3d.py:102-125) in eval mode on the channels-last tensor `a`: five launches, the q x k score matrix is never written."""
+    if a.dims[2] < 2 or a.dims[3] < 2:
+        raise ValueError("%s the block's (1,2,2) max-pool needs frames of at least 2 x 2, got %s" % (p, a.dims[2:],))
+    theta = P[p + "theta"](a, relu=False)                                                # :107
+    mp = E.maxpool(a, (1, 2, 2), (1, 2, 2))                                              # :95,106: floor semantics, an odd last row / column is dropped
+    pg = P[p + "phi_g"](mp, relu=False)                                                  # :108-109
+    d = nl.dim_inner
+    t = E.nl_attention(theta, pg.slice(0, d), pg.slice(d, d), float(d) ** -0.5)          # :112-119 (csrc/nonlocal.hip)
+    return P[p + "out"](t, residual=a, relu=False)                                       # :121-124: out + bn + residual, no ReLU
+
+
 class Bottleneck(nn.Module):
     """Parameter layout of large_i3d.py:42-84 (conv1 3x1x1|1x1x1, conv2 1x3x3, conv3 1x1x1)."""
     expansion = 4
 
-    def __init__(self, inplanes, planes, stride, has_down, temp_conv):
+    def __init__(self, inplanes, planes, stride, has_down, temp_conv, use_nl=False):
         super().__init__()
         self.conv1 = ConvParams(inplanes, planes, (1 + 2 * temp_conv, 1, 1), init="kaiming_fan_out")
         self.bn1 = BNParams(planes)
@@ -37,6 +85,7 @@ class Bottleneck(nn.Module):
             self.downsample = nn.Sequential(ConvParams(inplanes, planes * 4, (1, 1, 1), init="kaiming_fan_out"),
                                             BNParams(planes * 4))
         self.stride, self.temp_conv = stride, temp_conv
+        self.nl = NonLocalBlock(planes * 4, planes * 4, planes * 4 // 2) if use_nl else None      # large_i3d.py:57-58
 
 
 class I3Res50(nn.Module):
@@ -44,15 +93,16 @@ class I3Res50(nn.Module):
 
     def __init__(self, num_classes=400, use_nl=False, dtype=E.DEFAULT_DTYPE):
         super().__init__()
-        if use_nl:
-            raise NotImplementedError("NonLocalBlock is never enabled by the reference (model_loaders.py:262)")
+        self.use_nl = bool(use_nl)
         self.conv1 = ConvParams(3, 64, (5, 7, 7), init="kaiming_fan_out")
         self.bn1 = BNParams(64)
         inplanes = 64
         for li, (planes, blocks, stride, tc) in enumerate(LAYER_PLAN, 1):
             blks = []
             for i in range(blocks):
-                blks.append(Bottleneck(inplanes, planes, stride if i == 0 else 1, i == 0, tc[i]))
+                # nonlocal_mod = 2 on layer2 and layer3 only, never on a layer's block 0 (large_i3d.py:141-145,166-169)
+                nl = self.use_nl and li in (2, 3) and i >= 1 and i % 2 == 1
+                blks.append(Bottleneck(inplanes, planes, stride if i == 0 else 1, i == 0, tc[i], use_nl=nl))
                 inplanes = planes * 4
             setattr(self, "layer%d" % li, nn.Sequential(*blks))
         self.fc = LinearParams(2048, num_classes)
@@ -106,6 +156,8 @@ class I3Res50(nn.Module):
                             s3, b3 = self._bn_fold(blk.bn3)
                             P[p + "dual"] = E.PackedConv.fused_pair(blk.conv3.weight, s3, b3, blk.downsample[0].weight, s, b,
                                                                     dtype=self.compute_dtype, device=dev)
+                    if blk.nl is not None:
+                        pack_nonlocal(P, p + "nl.", blk.nl, self.compute_dtype, dev)
             for i in range(len(self.layer1) - 1):               # a plain layer1 tail that also emits the next block's conv1 (four-frame clips)
                 p, q = "layer1.%d." % i, "layer1.%d." % (i + 1)
                 w1 = self.layer1[i + 1].conv1.weight
@@ -175,6 +227,8 @@ class I3Res50(nn.Module):
                 bf = P.get(p + "frame") if taps is None else None
                 if bf is not None and bf.applies(a):
                     a = bf(a)                                             # conv1 -> conv2 -> conv3 + residual: only the block input and output touch HBM
+                    if blk.nl is not None:
+                        a = self._nonlocal(P, p, blk.nl, a, taps)
                     continue
                 tp = P.get(p + "conv1_tp") if taps is None else None
                 if h_next is not None:
@@ -202,16 +256,22 @@ class I3Res50(nn.Module):
                     else:
                         a = tail(h, pads=(0, 1, 1), residual=a, pool_t2=fuse_pool)
                         pooled = pooled or fuse_pool
+                    if blk.nl is not None:
+                        a = self._nonlocal(P, p, blk.nl, a, taps)
                     continue
                 h = P[p + "conv2"](h, pads=(0, 1, 1))
                 if blk.downsample is not None and taps is None and P[p + "conv3"].dual_supported(P[p + "down"], h, a):
                     # layer1.0: conv3 + bn3 and the downsample branch in one launch (the 256-channel downsample tensor
                     # is never written; both branches stay fp32 until the sum)
                     a = P[p + "conv3"].call_dual(h, P[p + "down"], a, relu=True)
+                    if blk.nl is not None:
+                        a = self._nonlocal(P, p, blk.nl, a, taps)
                     continue
                 if (p + "dual") in P and taps is None and P[p + "dual"].dual_p8_supported(h, a, (blk.stride, blk.stride)):
                     # layer2.0 / 3.0 / 4.0: the same pair as ONE GEMM over [W3*s3 | Wd*sd] on the ping-pong kernel
                     a = P[p + "dual"].call_dual_p8(h, a, (blk.stride, blk.stride), relu=True)
+                    if blk.nl is not None:
+                        a = self._nonlocal(P, p, blk.nl, a, taps)
                     continue
                 res = P[p + "down"](a, relu=False) if blk.downsample is not None else a
                 if li == 1 and i == len(layer) - 1 and taps is None and P[p + "conv3"].pool_t2_supported(h):
@@ -221,10 +281,18 @@ class I3Res50(nn.Module):
                     pooled = True
                 else:
                     a = P[p + "conv3"](h, residual=res, relu=True)       # bn3 + (+= residual) + ReLU fused
+                if blk.nl is not None:
+                    a = self._nonlocal(P, p, blk.nl, a, taps)
             if taps is not None:
                 taps["layer%d" % li] = a
             if self.check_saturation:
                 self._sat = E.count_saturated(a, self._sat)
+        return a
+
+    def _nonlocal(self, P, p, nl, a: E.Act, taps=None) -> E.Act:
+        a = nonlocal_forward(P, p + "nl.", nl, a)
+        if taps is not None:
+            taps[p + "nl"] = a
         return a
 
     # ---- f16 head-room, observable -----------------------------------------------------------------------------------

@@ -4,7 +4,7 @@ the networks running on MI355X HIP kernels (libtedspad_hip.so).
 
     load_fa_model(saved_model_file=None, arch='unet++')                       model_loaders.py:17-52
     load_ft_model(arch='r3d', saved_model_file=None, num_classes=400,
-                  kin_pretrained=False)                                       model_loaders.py:56-90
+                  kin_pretrained=False, use_nl=False)                         model_loaders.py:56-90 (+ use_nl: large_i3d.py:132)
     mlp, wrapper_i3d                                                          model_loaders.py:235-268
 
 In scope: arch 'largei3d' and 'i3d' for ft, 'unet' for fa (the architectures whose source is part of the reference), 'unet++' for
@@ -54,9 +54,10 @@ class mlp(nn.Module):
 class wrapper_i3d(nn.Module):
     """model_loaders.py:258-268: returns (pred, mlp(feature)); keys `i3d.*`, `mlp.*`."""
 
-    def __init__(self, num_classes=102, dtype=E.DEFAULT_DTYPE):
+    def __init__(self, num_classes=102, dtype=E.DEFAULT_DTYPE, use_nl=False):
+        """use_nl: build the trunk with its non-local blocks (large_i3d.py:132; the reference's wrapper passes False, :262) -- inference only."""
         super().__init__()
-        self.i3d = I3Res50(num_classes=num_classes, use_nl=False, dtype=dtype)
+        self.i3d = I3Res50(num_classes=num_classes, use_nl=use_nl, dtype=dtype)
         self.mlp = mlp()
 
     def forward(self, x):
@@ -92,11 +93,11 @@ def build_i3d_classifier(num_classes=400, pretrained=True):
                                 lambda m, n: m.replace_logits(n), num_classes, pretrained)
 
 
-def build_largei3d_classifier(num_classes=400, pretrained=True):
+def build_largei3d_classifier(num_classes=400, pretrained=True, use_nl=False):
     """model_loaders.py:185-196: wrapper_i3d around I3Res50, `i3d_r50_kinetics.pth` loaded into `.i3d`, a fresh `fc` for the new classes."""
     def new_fc(m, n):
         m.i3d.fc = LinearParams(512 * 4, n)
-    return _kinetics_classifier(lambda n: wrapper_i3d(num_classes=n), "i3d_r50_kinetics.pth", lambda m: m.i3d, new_fc, num_classes, pretrained)
+    return _kinetics_classifier(lambda n: wrapper_i3d(num_classes=n, use_nl=use_nl), "i3d_r50_kinetics.pth", lambda m: m.i3d, new_fc, num_classes, pretrained)
 
 
 def _strip_module(sd):
@@ -127,11 +128,15 @@ def load_fa_model(saved_model_file=None, arch="unet++"):
     return fa_model
 
 
-def load_ft_model(arch="r3d", saved_model_file=None, num_classes=400, kin_pretrained=False):
+def load_ft_model(arch="r3d", saved_model_file=None, num_classes=400, kin_pretrained=False, use_nl=False):
+    """use_nl (not in the reference's factory, whose wrapper fixes it to False): 'largei3d' with the non-local blocks of large_i3d.py:86-125, so that a
+    checkpoint with `i3d.layer2.1.nl.*` keys loads; inference only."""
+    if use_nl and arch != "largei3d":
+        raise NotImplementedError("use_nl=True: only arch 'largei3d' has non-local blocks")
     if arch == "i3d":
         ft_model = build_i3d_classifier(num_classes=num_classes, pretrained=kin_pretrained)
     elif arch == "largei3d":
-        ft_model = build_largei3d_classifier(num_classes=num_classes, pretrained=kin_pretrained)
+        ft_model = build_largei3d_classifier(num_classes=num_classes, pretrained=kin_pretrained, use_nl=use_nl)
     elif arch in ("mvitv2", "r3d_18"):
         raise NotImplementedError("arch '%s' is a torchvision model (third-party): out of scope." % arch)
     else:

@@ -290,6 +290,8 @@ def _bottleneck_blocks(layers, dt, temporal):
 
 class I3DTrainer:
     def __init__(self, wrapper):
+        from .i3res50 import refuse_nonlocal_training
+        refuse_nonlocal_training(wrapper, "I3DTrainer")
         self.m = wrapper
         i3d = wrapper.i3d
         dt = i3d.compute_dtype

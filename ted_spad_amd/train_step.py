@@ -325,6 +325,8 @@ class ClipUtility:
 
 class AnonymizerTrainStep(ClipUtility, StepDriver):
     def __init__(self, fa_model, ft_model, params=DEFAULT_PARAMS, fb_model=None, group=None, loss_scale: float = 256.0):
+        from .i3res50 import refuse_nonlocal_training
+        refuse_nonlocal_training(ft_model, "AnonymizerTrainStep")
         StepDriver.__init__(self, loss_scale)
         self.fa, self.fb = fa_model, fb_model
         self.batch_views = os.environ.get("TEDSPAD_TRAIN_BATCH_VIEWS", "1") != "0"   # the two VISPR views as one fa / fb batch with per-view statistics (0: two passes)
@@ -576,7 +578,9 @@ class ActionTrainStep(ClipUtility, StepDriver):
 
     def __init__(self, ft_model, fa_model=None, params=DEFAULT_ACTION_PARAMS, opt_type=None, loss_scale="dynamic", group=None):
         from .optim import DynamicLossScale, FusedOptimizer
+        from .i3res50 import refuse_nonlocal_training
         p = params
+        refuse_nonlocal_training(ft_model, "ActionTrainStep")
         if getattr(p, "arch", "largei3d") != "largei3d":
             raise NotImplementedError("ActionTrainStep: arch %r is not implemented (only 'largei3d')" % p.arch)
         if p.loss != "ce":
