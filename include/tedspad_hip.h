@@ -910,6 +910,29 @@ int32_t tedspad_optim_finish(int32_t *state, float *scale_state, double beta1, d
 int32_t tedspad_nl_attention_fwd(const void *theta, int32_t ld_theta, const void *phi, int32_t ld_phi, const void *g, int32_t ld_g, void *out, int32_t ld_out,
                                  int32_t n, int32_t q, int32_t k, int32_t d, float scale, int32_t dtype, void *stream);
 
+/* ---- the same with a tape, and its backward (csrc/nonlocal.hip) ----
+ * tedspad_nl_attention_fwd_lse is tedspad_nl_attention_fwd (the same kernel, `out` bit-identical) with one more output: lse (n, q) fp32,
+ *   lse[b, i] = ln sum_j exp(scale * theta[b, i, :] . phi[b, j, :])        (the running maximum included)
+ * tedspad_nl_attention_bwd takes theta, phi, g, the forward's out `t`, the upstream gradient `dt` (n, q, d) and lse, and writes
+ *   P = exp(scale theta phi^T - lse)     recomputed, never written
+ *   dg = P^T dt        D_i = sum_c dt[i, c] t[i, c]        dS = P o (dt g^T - D)        dtheta = scale dS phi        dphi = scale dS^T theta
+ * as 16-bit rows with their own strides (dphi | dg may be the two channel halves of one buffer, as phi | g may be). P and dS are rounded to the storage
+ * type for the second products, every sum is fp32, every output is rounded once. All of these conversions are the training path's: none clamps, so a
+ * dS or a result past the f16 range, and a non-finite dt or lse, reach the gradients as inf / NaN (for a loss scale's non-finite check to find).
+ * f16 and small values: gfx950's matrix cores flush f16 SUBNORMAL operands, so a P below 2^-14 = 6.1e-5 (a key more than 9.7 below the row's
+ * log-sum-exp; with 392 equally weighted keys every P is 2.6e-3) and a dS below it contribute nothing to dg / dtheta / dphi: the error of a term is
+ * u * P only above that floor. Pass dt SCALED (the autograd bridge multiplies by 256, a loss scale does the same) so that dS stays normal; bf16 has
+ * fp32's range and no such floor. Three launches (D, one workgroup per 32 keys for
+ * dphi and dg, one per 32 queries for dtheta), no atomics: every result depends on its own batch item alone and is bit-identical from run to run and in
+ * any batch. `workspace` holds D: tedspad_nl_attention_bwd_workspace (HOST side, pure CPU) gives its size in bytes. Shapes, alignment and the error for
+ * d other than 256 / 512 as in the forward; no output aliases another argument. */
+int32_t tedspad_nl_attention_fwd_lse(const void *theta, int32_t ld_theta, const void *phi, int32_t ld_phi, const void *g, int32_t ld_g, void *out,
+                                     int32_t ld_out, float *lse, int32_t n, int32_t q, int32_t k, int32_t d, float scale, int32_t dtype, void *stream);
+int32_t tedspad_nl_attention_bwd_workspace(int32_t n, int32_t q, int64_t *bytes);
+int32_t tedspad_nl_attention_bwd(const void *theta, int32_t ld_theta, const void *phi, int32_t ld_phi, const void *g, int32_t ld_g, const void *t, int32_t ld_t,
+                                 const void *dt, int32_t ld_dt, const float *lse, void *dtheta, int32_t ld_dtheta, void *dphi, int32_t ld_dphi, void *dg,
+                                 int32_t ld_dg, void *workspace, int32_t n, int32_t q, int32_t k, int32_t d, float scale, int32_t dtype, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -173,6 +173,9 @@ SYMBOLS = {
     "tedspad_optim_update": (_I32, [_P, _I32, _I32, _P, _P, C.c_float, C.c_double, C.c_double, C.c_float, C.c_float, C.c_float, _P]),
     "tedspad_optim_finish": (_I32, [_P, _P, C.c_double, C.c_double, C.c_float, C.c_float, _I32, _P, _P]),
     "tedspad_nl_attention_fwd": (_I32, [_P, _I32, _P, _I32, _P, _I32, _P, _I32, _I32, _I32, _I32, _I32, C.c_float, _I32, _P]),
+    "tedspad_nl_attention_fwd_lse": (_I32, [_P, _I32, _P, _I32, _P, _I32, _P, _I32, _P, _I32, _I32, _I32, _I32, C.c_float, _I32, _P]),
+    "tedspad_nl_attention_bwd_workspace": (_I32, [_I32, _I32, C.POINTER(_I64)]),
+    "tedspad_nl_attention_bwd": (_I32, [_P, _I32] * 5 + [_P] + [_P, _I32] * 3 + [_P, _I32, _I32, _I32, _I32, C.c_float, _I32, _P]),
 }
 
 _lib = None

@@ -278,3 +278,68 @@ def freeze_bn(model):
     refuse_nonlocal_training(model, "freeze_bn")
     target.frozen_bn = True
     return model
+
+
+# ---- NonLocalBlock ---------------------------------------------------------------------------------------------------------------
+
+class _NonLocalFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, trainer, mode, x, *params):
+        ctx.tape_guard = _Tape(x.device)
+        y, tape = trainer.forward(_nl_act(x, trainer.m.compute_dtype, 1.0), mode)
+        ctx.trainer, ctx.tape, ctx.need_dx = trainer, tape, x.requires_grad
+        ctx.set_materialize_grads(False)
+        return E.act_to_nchw(y)
+
+    @staticmethod
+    def backward(ctx, dy):
+        tr = ctx.trainer
+        params = list(tr.m.parameters())
+        if dy is None:
+            return (None, None, None) + (None,) * len(params)
+        ctx.tape_guard.check()
+
+        def run():
+            dx = tr.backward(ctx.tape, _nl_act(dy, tr.m.compute_dtype, TE.GRAD_SCALE))
+            tr.flush_grads()
+            return E.act_to_nchw(dx) if ctx.need_dx else None
+
+        dx, grads = _capture_grads(params, run)
+        ctx.tape = None
+        return (None, None, _down(dx)) + tuple(_down(grads))      # 'frozen': nothing was accumulated for bn.weight / bn.bias, they stay None
+
+
+def _nl_act(x, dtype, scale):
+    """fp32 (n, c, t, h, w) -> the 16-bit channels-last Act of the block (a layout change and one rounding; no arithmetic of the block)."""
+    x = x.detach().permute(0, 2, 3, 4, 1)
+    if scale != 1.0:
+        x = x * scale
+    return E.Act(x.to(E.DTYPES[dtype][0]).contiguous(), x.shape[4])
+
+
+def nonlocal_block_forward(module, x):
+    """NonLocalBlock.forward (large_i3d.py:102-125) on fp32 (n, c, t, h, w): train() -> batch-statistics bn, running statistics and num_batches_tracked
+    moved as nn.BatchNorm3d moves them, every parameter's gradient and the input's; eval() with gradients -> bn as the fixed affine of its running
+    statistics ('frozen': gamma / beta get no gradient); eval() under no_grad -> the packed inference sequence (i3res50.nonlocal_forward)."""
+    from .i3res50 import nonlocal_forward, pack_nonlocal
+    from .params import params_signature
+    from .train_nets import NonLocalTrainer
+    E.require_cuda(x, "NonLocalBlock")
+    if x.dim() != 5 or x.shape[1] != module.dim_in:
+        raise ValueError("NonLocalBlock: expected (n, %d, t, h, w), got %s" % (module.dim_in, tuple(x.shape)))
+    if not module.training and not torch.is_grad_enabled():
+        sig = (params_signature(module), module.compute_dtype)
+        if module.__dict__.get("_packed_sig") != sig:
+            P = {}
+            pack_nonlocal(P, "", module, module.compute_dtype, x.device)
+            module.__dict__["_packed"], module.__dict__["_packed_sig"] = P, sig
+        return E.act_to_nchw(nonlocal_forward(module.__dict__["_packed"], "", module, _nl_act(x, module.compute_dtype, 1.0)))
+    tr = _trainer(module, NonLocalTrainer)
+    if not torch.is_grad_enabled():                          # train() under no_grad: the statistics move, nothing is kept
+        guard = _Tape(x.device)                              # recycles the zero arena like any other forward (no tape of an earlier iteration alive)
+        y, _ = tr.forward(_nl_act(x, module.compute_dtype, 1.0), "train")
+        TE.flush_deferred()
+        out = E.act_to_nchw(y)
+        del guard
+        return out
+    return _NonLocalFn.apply(tr, "train" if module.training else "frozen", x, *module.parameters())

@@ -1006,10 +1006,12 @@ def maxpool(x: Act, k, s, pads=(0, 0, 0), pads_back=None, pad_zero=False, out: O
     return (out, idx) if return_idx else out
 
 
-def nl_attention(theta: Act, phi: Act, g: Act, scale: float, out: Optional[Act] = None) -> Act:
+def nl_attention(theta: Act, phi: Act, g: Act, scale: float, out: Optional[Act] = None, lse: Optional[torch.Tensor] = None) -> Act:
     """out[b, i, :] = sum_j softmax_j(scale * theta[b, i, :] . phi[b, j, :]) g[b, j, :] over the pixels of a batch item (large_i3d.py:112-119), one launch of
     tedspad_nl_attention_fwd: the score matrix is never written. theta (n, t, h, w, d) are the queries; phi and g (n, t, h', w', d) the keys and values, each
-    an Act with its own row stride and channel offset (two slices of one buffer). d: 256 or 512 -- any other width is the library's error, never a torch path."""
+    an Act with its own row stride and channel offset (two slices of one buffer). d: 256 or 512 -- any other width is the library's error, never a torch path.
+    lse: an fp32 (n, q) tensor that receives the log-sum-exp of the scaled logits (tedspad_nl_attention_fwd_lse, the tape of `nl_attention_bwd`); `out` is
+    bit-identical with and without it."""
     n, t, h, w = theta.dims
     assert phi.dims == g.dims and phi.dims[0] == n and theta.c == phi.c == g.c, "nl_attention: theta %s x %d, phi %s x %d, g %s x %d" % (
         theta.dims, theta.c, phi.dims, phi.c, g.dims, g.c)
@@ -1023,9 +1025,48 @@ def nl_attention(theta: Act, phi: Act, g: Act, scale: float, out: Optional[Act] 
     for n0 in range(0, n, nc):
         n1 = min(n, n0 + nc)
         ts, ps, gs, os_ = (Act(a.buf[n0:n1], a.c, a.coff) for a in (theta, phi, g, out))
-        check(_lib.lib().tedspad_nl_attention_fwd(ts.ptr, ts.ld, ps.ptr, ps.ld, gs.ptr, gs.ld, os_.ptr, os_.ld, n1 - n0, q, k, theta.c, C.c_float(scale), code,
-                                                  _stream_ptr()), "tedspad_nl_attention_fwd")
+        if lse is None:
+            check(_lib.lib().tedspad_nl_attention_fwd(ts.ptr, ts.ld, ps.ptr, ps.ld, gs.ptr, gs.ld, os_.ptr, os_.ld, n1 - n0, q, k, theta.c, C.c_float(scale), code,
+                                                      _stream_ptr()), "tedspad_nl_attention_fwd")
+        else:
+            assert lse.dtype == torch.float32 and lse.is_contiguous() and tuple(lse.shape) == (n, q)
+            check(_lib.lib().tedspad_nl_attention_fwd_lse(ts.ptr, ts.ld, ps.ptr, ps.ld, gs.ptr, gs.ld, os_.ptr, os_.ld, lse[n0:n1].data_ptr(), n1 - n0, q, k,
+                                                          theta.c, C.c_float(scale), code, _stream_ptr()), "tedspad_nl_attention_fwd_lse")
     return out
+
+
+def nl_attention_lse(theta: Act, phi: Act, g: Act, scale: float):
+    """`nl_attention` with its tape: (T, lse), lse (n, q) fp32."""
+    n, t, h, w = theta.dims
+    lse = torch.empty((n, t * h * w), dtype=torch.float32, device=theta.buf.device)
+    return nl_attention(theta, phi, g, scale, lse=lse), lse
+
+
+def nl_attention_bwd(theta: Act, phi: Act, g: Act, t: Act, lse: torch.Tensor, dt: Act, scale: float):
+    """Backward of `nl_attention` (tedspad_nl_attention_bwd): (dtheta, dphi, dg) as Acts of the inputs' shapes from the forward's inputs, its output `t`, its
+    `lse` and the upstream gradient `dt`. P is recomputed from lse; neither it nor dS is written. dt is expected SCALED (train_engine.GRAD_SCALE, a loss
+    scale): the matrix cores flush f16 subnormal operands, and nothing is clamped -- an overflow comes back as inf / NaN."""
+    n, tt, h, w = theta.dims
+    d = theta.c
+    assert phi.dims == g.dims and t.dims == theta.dims == dt.dims and phi.c == g.c == t.c == dt.c == d
+    q, k = tt * h * w, phi.dims[1] * phi.dims[2] * phi.dims[3]
+    assert lse.dtype == torch.float32 and lse.is_contiguous() and tuple(lse.shape) == (n, q)
+    tdt, dev = theta.buf.dtype, theta.buf.device
+    code = _lib.F16 if tdt == torch.float16 else _lib.BF16
+    dtheta = Act.empty(n, tt, h, w, d, tdt, dev)
+    dphi, dg = Act.empty(*phi.dims, d, tdt, dev), Act.empty(*phi.dims, d, tdt, dev)
+    nbytes = C.c_int64(0)
+    check(_lib.lib().tedspad_nl_attention_bwd_workspace(n, q, C.byref(nbytes)), "tedspad_nl_attention_bwd_workspace")
+    ws = torch.empty(nbytes.value // 4, dtype=torch.float32, device=dev)
+    acts = (theta, phi, g, t, dt, dtheta, dphi, dg)
+    nc = batch_chunk(n, [q * max(a.ld for a in (theta, t, dt, dtheta)), k * max(a.ld for a in (phi, g, dphi, dg))], MAX_ELEMS)
+    for n0 in range(0, n, nc):
+        n1 = min(n, n0 + nc)
+        s = [Act(a.buf[n0:n1], a.c, a.coff) for a in acts]
+        check(_lib.lib().tedspad_nl_attention_bwd(s[0].ptr, s[0].ld, s[1].ptr, s[1].ld, s[2].ptr, s[2].ld, s[3].ptr, s[3].ld, s[4].ptr, s[4].ld,
+                                                  lse[n0:n1].data_ptr(), s[5].ptr, s[5].ld, s[6].ptr, s[6].ld, s[7].ptr, s[7].ld, ws.data_ptr(), n1 - n0, q, k, d,
+                                                  C.c_float(scale), code, _stream_ptr()), "tedspad_nl_attention_bwd")
+    return dtheta, dphi, dg
 
 
 def global_avgpool(x: Act) -> torch.Tensor:

@@ -22,16 +22,23 @@ LAYER_PLAN = ((64, 3, 1, (1, 1, 1)), (128, 4, 2, (1, 0, 1, 0)), (256, 6, 2, (1, 
 
 class NonLocalBlock(nn.Module):
     """Parameter layout of large_i3d.py:86-100: theta / phi / g (dim_in -> dim_inner) and out (dim_inner -> dim_out) are 1x1x1 convolutions WITH bias,
-    bn a BatchNorm3d(dim_out); the max-pool in front of phi and g has no parameters. Inference only: `nonlocal_forward` is its launch sequence."""
+    bn a BatchNorm3d(dim_out); the max-pool in front of phi and g has no parameters. Inside I3Res50 the block is inference only (`nonlocal_forward` is its
+    launch sequence there); on its own it is a differentiable module: `forward` is the reference's (large_i3d.py:102-125) on fp32 (n, c, t, h, w), in
+    train() and eval(), through `autograd.nonlocal_block_forward`."""
 
-    def __init__(self, dim_in, dim_out, dim_inner):
+    def __init__(self, dim_in, dim_out, dim_inner, dtype=E.DEFAULT_DTYPE):
         super().__init__()
         self.dim_in, self.dim_inner, self.dim_out = dim_in, dim_inner, dim_out
+        self.compute_dtype = dtype
         self.theta = ConvParams(dim_in, dim_inner, (1, 1, 1), bias=True, init="kaiming_fan_out")
         self.phi = ConvParams(dim_in, dim_inner, (1, 1, 1), bias=True, init="kaiming_fan_out")
         self.g = ConvParams(dim_in, dim_inner, (1, 1, 1), bias=True, init="kaiming_fan_out")
         self.out = ConvParams(dim_inner, dim_out, (1, 1, 1), bias=True, init="kaiming_fan_out")
         self.bn = BNParams(dim_out)
+
+    def forward(self, x):
+        from .autograd import nonlocal_block_forward
+        return nonlocal_block_forward(self, x)
 
 
 def has_nonlocal(model) -> bool:

@@ -893,3 +893,75 @@ class UNetPPTrainer:
         d = TE.maxpool_bwd(tape["f1"], tape["idx1"], d, (1, 3, 3), (1, 2, 2), pads=(0, 1, 1), add=G["f1"])
         TE.conv_bn_act_train_bwd(tape["stem"], d, need_dx=False)
         done(10, [self.stem])
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# NonLocalBlock (large_i3d.py:86-125) as a block: forward with tape and backward
+# ------------------------------------------------------------------------------------------------------------------
+
+class NonLocalTrainer:
+    """theta | pool -> phi, g | attention | out + bn + residual, with tape, and its backward. Modes:
+       'train' : batch-statistics bn (running statistics moved once per forward), every parameter gets its gradient
+       'frozen': bn is the fixed affine of its running statistics (gamma / beta get no gradient), the four convolutions get theirs
+    Both return the gradient w.r.t. the block input: the residual path + theta's data gradient + the pool's backward of phi's and g's.
+    The attention core and its backward are csrc/nonlocal.hip (the score matrix is written in neither direction); everything around it is what
+    `train_engine` has."""
+    POOL = ((1, 2, 2), (1, 2, 2))
+
+    def __init__(self, block):
+        self.m = block
+        dt = block.compute_dtype
+        self.theta, self.phi, self.g, self.out = (TE.ConvLayer(c.weight, c.bias, dtype=dt) for c in (block.theta, block.phi, block.g, block.out))
+        self.scale = float(block.dim_inner) ** -0.5
+        self._folds = {}
+
+    def conv_layers(self):
+        return [self.theta, self.phi, self.g, self.out]
+
+    def flush_grads(self):
+        TE.flush_conv_grads(self.conv_layers())
+
+    def grad_buckets(self):
+        """One group: every gradient of the block is final when `backward` returns."""
+        return [list(self.m.parameters())]
+
+    def forward(self, a: Act, mode: str, groups: int = 1):
+        """a: the block input (n, t, h, w, dim_in), 16-bit channels-last. Returns (y, tape); y = bn(out(attention)) + a, no ReLU (large_i3d.py:121-124).
+        groups ('train'): `groups` consecutive blocks of samples, each with its own batch statistics (TE.conv_bn_act_train)."""
+        assert mode in ("train", "frozen")
+        if a.dims[2] < 2 or a.dims[3] < 2:
+            raise ValueError("NonLocalBlock: the (1,2,2) max-pool needs frames of at least 2 x 2, got %s" % (a.dims[2:],))
+        bn = self.m.bn
+        theta = self.theta.forward(a)                                                  # :107
+        mp, idx = E.maxpool(a, *self.POOL, return_idx=True)                            # :95,106
+        phi, g = self.phi.forward(mp), self.g.forward(mp)                              # :108-109
+        t, lse = E.nl_attention_lse(theta, phi, g, self.scale)                         # :112-119
+        tape = dict(mode=mode, a=a, mp=mp, idx=idx, theta=theta, phi=phi, g=g, t=t, lse=lse)
+        if mode == "train":
+            y, tape["bn"] = TE.conv_bn_act_train(self.out, bn, t, relu=False, residual=a, groups=groups)      # :121-124
+            TE.flush_counters()
+        else:
+            s, b = TE.cached_fold(self._folds, bn, conv_bias=self.m.out.bias)
+            y = self.out.forward(t, scale=s, shift=b, relu=False, residual=a)
+            tape["s"] = s
+        return y, tape
+
+    def backward(self, tape, dy: Act) -> Act:
+        """dy: the gradient w.r.t. the block output. Accumulates the parameter gradients (flush_grads() moves the convolutions' into .grad) and
+        returns the gradient w.r.t. the block input."""
+        a, mp, t = tape["a"], tape["mp"], tape["t"]
+        if tape["mode"] == "train":
+            dt, dres = TE.conv_bn_act_train_bwd(tape["bn"], dy)
+        else:
+            s = tape["s"]
+            # d(out's output) = dy * s per channel: the packed accumulator takes wgrad(t, dy) and its rows are scaled at the flush; the bias by hand
+            self.out.wgrad(t, dy, db=TE.channel_sums(dy)[0] * s[:dy.c])
+            self.out._grad_row_scale = s
+            dt, dres = self.out.dgrad(dy, t.dims[1:], scale=s), dy
+        dtheta, dphi, dg = E.nl_attention_bwd(tape["theta"], tape["phi"], tape["g"], t, tape["lse"], dt, self.scale)
+        self.theta.wgrad(a, dtheta)
+        self.phi.wgrad(mp, dphi)
+        self.g.wgrad(mp, dg)
+        dmp = self.g.dgrad(dg, mp.dims[1:], residual=self.phi.dgrad(dphi, mp.dims[1:]))
+        dpool = TE.maxpool_bwd(a, tape["idx"], dmp, *self.POOL, add=dres)              # an odd last row / column: no pooled pixel reads it, zero
+        return self.theta.dgrad(dtheta, a.dims[1:], residual=dpool)
