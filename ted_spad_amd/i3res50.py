@@ -176,6 +176,27 @@ class I3Res50(nn.Module):
         return self._packed
 
     # ---- the launch sequence ---------------------------------------------------------------
+    def _check_geometry(self, frames: int, h: int, w: int, shape) -> None:
+        """Refuses, before anything is launched, the clips the reference itself cannot process: its pooling layers raise on an input smaller than their
+        window (large_i3d.py:138 maxpool1, :139 maxpool2, :95 the non-local blocks' pool), where the launches below would compute an empty tensor.
+        frames: what maxpool1 leaves of the clip's T; (h, w): the clip's frame size."""
+        h, w = E.conv_out(h, 7, 2, 3, 3), E.conv_out(w, 7, 2, 3, 3)
+        if h < 3 or w < 3:
+            raise ValueError("I3Res50: maxpool1's 3 x 3 window needs a conv1 output of at least 3 x 3, that is frames of at least 5 x 5 pixels; "
+                             "got %s" % (shape,))
+        if frames < 2:
+            raise ValueError("I3Res50: maxpool2 pools over frame pairs behind maxpool1, which takes clips of at least 7 frames (two frame pairs of stem "
+                             "records); got %s" % (shape,))
+        h, w = E.conv_out(h, 3, 2, 0, 0), E.conv_out(w, 3, 2, 0, 0)
+        for li in range(1, 5):
+            layer = getattr(self, "layer%d" % li)
+            if len(layer):
+                s = layer[0].stride
+                h, w = E.conv_out(h, 3, s, 1, 1), E.conv_out(w, 3, s, 1, 1)
+            if any(blk.nl is not None for blk in layer) and (h < 2 or w < 2):
+                raise ValueError("I3Res50: the non-local blocks' (1,2,2) max-pool needs frames of at least 2 x 2, layer%d's are %d x %d; got %s" % (
+                    li, h, w, shape))
+
     def _trunk(self, x: torch.Tensor, taps=None, records: torch.Tensor = None) -> E.Act:
         """conv1 .. layer4 (large_i3d.py:229-238 == :251-260) on a (B,3,T,H,W) fp32 clip batch -- or, with `records`, on the persistent stem's own 16-bit input
         layout X[n][tp][h][2][w/2][24] (engine.StemPT.layout; preprocess.crop_resize_records writes it straight from uint8 frames)."""
@@ -193,6 +214,7 @@ class I3Res50(nn.Module):
                 raise ValueError("expected contiguous stem records (n, frame pairs, h, 2, w/2, 24) of %s, got %s %s" % (st.torch_dtype, tuple(records.shape), records.dtype))
             if records.shape[1] < 1 or (records.shape[2] + 1) // 2 < 3 or records.shape[4] < 3:
                 raise ValueError("stem records need at least one frame pair and frames of 5 x 6 pixels for conv1 + maxpool1, got %s" % (tuple(records.shape),))
+            self._check_geometry(int(records.shape[1]), int(records.shape[2]), 2 * int(records.shape[4]), tuple(records.shape))
             a = st.conv_pool(records)                                    # conv1 + bn1 + ReLU + maxpool1 from the records (the LDS-DMA loader of csrc/conv_stem_pt.hip)
             x = None
         else:
@@ -201,6 +223,7 @@ class I3Res50(nn.Module):
                 raise ValueError("expected (B,3,T,H,W), got %s" % (tuple(x.shape),))
             if x.shape[4] % 2:
                 raise ValueError("W must be even")
+            self._check_geometry(E.conv_out(int(x.shape[2]), 5, 2, 2, 2) // 2, int(x.shape[3]), int(x.shape[4]), tuple(x.shape))
         if records is not None:
             pass
         elif E.STEM_PT and taps is None and P["stem_pt"].applies(x):
