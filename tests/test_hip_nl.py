@@ -105,8 +105,12 @@ def run_kernel(name, variant, dtype):
     return got, ref, g
 
 
+def fwd_bound(g, dtype):
+    return 4.0 * U[dtype] * g.double().abs().amax(dim=1, keepdim=True)           # per batch item and channel
+
+
 def check_bound(got, ref, g, dtype, what):
-    bound = 4.0 * U[dtype] * g.double().abs().amax(dim=1, keepdim=True)          # per batch item and channel
+    bound = fwd_bound(g, dtype)
     err = (got - ref).abs()
     worst = float((err / bound.clamp_min(1e-30)).max())
     print("%s %s: max |err| / (4 u max|g|) = %.3f, max |err| = %.3e" % (what, dtype, worst, float(err.max())))

@@ -38,60 +38,124 @@ def upstream(name, variant, dtype):
     return synth_tensor(7, "%s/%s/dt" % (name, variant), (n, qk(SHAPES[name])[0], d), -1.0, 1.0).to(tdt_of(dtype)).float()
 
 
-def run(theta, phi, g, dt, dtype, sliced):
-    """tedspad_nl_attention_fwd, _fwd_lse and _bwd on fresh buffers: every output row is padded (ld = d + 8, or the 2 d + 8 of a shared dphi | dg buffer)
-    and followed by guard rows; the padding and the guards must come back untouched. Returns raw 16-bit images (n, rows, d) and float64 copies."""
+QUIET_NAN = {"f16": 0x7E00, "bf16": 0x7FC0}
+
+
+def run(theta, phi, g, dt, dtype, sliced, scale=None, ld=None, poison=False, tape=None):
+    """tedspad_nl_attention_fwd, _fwd_lse and _bwd on fresh buffers. Every buffer has GUARD_ROWS rows in front of its first and behind its last row; every
+    output row is padded (ld = d + 8, or the 2 d + 8 of a shared dphi | dg buffer). The outputs' padding, the channels of a shared output buffer that belong
+    to neither slice and the guards -- the guard floats around lse and the workspace too -- must come back untouched. Returns raw 16-bit images
+    (n * rows, d) and float64 copies.
+      scale    the softmax scale (default d ** -0.5)
+      ld       every operand's row stride, overriding the defaults: {"theta", "dt", "t", "dtheta": ld}, {"phi", "g": ld} or {"pg": (ld, g's channel offset)}
+               for phi and g as slices of one buffer, {"dphi", "dg": ld} or {"dpg": (ld, dg's channel offset)}
+      poison   the padding, the guard rows and the unused channels of every INPUT (of the backward's T and lse as well) hold the storage type's quiet NaN
+      tape     (T as an (n * q, d) 16-bit image, lse (n, q) fp32) from the host for the backward, instead of the forward kernel's own"""
     from ted_spad_amd import _lib
     from ted_spad_amd.engine import _stream_ptr
     n, q, d = theta.shape
     k = phi.shape[1]
     tdt, code = (torch.float16, _lib.F16) if dtype == "f16" else (torch.bfloat16, _lib.BF16)
-    scale = C.c_float(float(d) ** -0.5)
+    scale = C.c_float(float(d) ** -0.5 if scale is None else scale)
     lib, sp = _lib.lib(), _stream_ptr()
-    th, dtd = theta.to(tdt).cuda(), dt.to(tdt).cuda()
-    if sliced:
-        pg = torch.cat([phi, g], dim=2).to(tdt).cuda().contiguous()
-        pp, gp, ldp, ldg = pg.data_ptr(), pg.data_ptr() + 2 * d, 2 * d, 2 * d
+    L = dict(theta=d, dt=d, t=d + 8, dtheta=d + 8)
+    L.update(dict(pg=(2 * d, d), dpg=(2 * d + 8, d)) if sliced else dict(phi=d, g=d, dphi=d + 8, dg=d + 8))
+    if ld is not None:
+        for pair, one in (("pg", ("phi", "g")), ("dpg", ("dphi", "dg"))):
+            if pair in ld or one[0] in ld:                # the caller chooses between one buffer and two
+                for key in (pair,) + one:
+                    L.pop(key, None)
+        L.update(ld)
+    fill = QUIET_NAN[dtype] if poison else 0
+    G = GUARD_ROWS
+
+    def source(rows, width, *parts):
+        """A (G + rows + G, width) input image holding `parts` [(values (n, r, d), first channel)]; its first row's address."""
+        host = torch.full((rows + 2 * G, width), fill, dtype=torch.int16)
+        for x, c0 in parts:
+            host[G:G + rows, c0:c0 + d] = x.to(tdt).view(torch.int16).reshape(rows, d)
+        dev = host.cuda()
+        return dev, dev.data_ptr() + G * width * 2
+
+    def sink(rows, width):
+        dev = torch.full((rows + 2 * G, width), SENTINEL, dtype=torch.int16, device="cuda")
+        return dev, dev.data_ptr() + G * width * 2
+
+    floats = lambda: torch.full((n * q + 2 * G,), LSE_GUARD, dtype=torch.float32, device="cuda")
+    th, thp = source(n * q, L["theta"], (theta, 0))
+    dtd, dtp = source(n * q, L["dt"], (dt, 0))
+    if "pg" in L:
+        ldp = ldg = L["pg"][0]
+        pg, pp = source(n * k, ldp, (phi, 0), (g, L["pg"][1]))
+        gp = pp + 2 * L["pg"][1]
     else:
-        ph, gg = phi.to(tdt).cuda(), g.to(tdt).cuda()
-        pp, gp, ldp, ldg = ph.data_ptr(), gg.data_ptr(), d, d
-    ldo = d + 8
-    buf = lambda rows, ld: torch.full((rows + GUARD_ROWS, ld), SENTINEL, dtype=torch.int16, device="cuda")
-    out0, out1, dth = buf(n * q, ldo), buf(n * q, ldo), buf(n * q, ldo)
-    lse = torch.full((n * q + GUARD_ROWS,), LSE_GUARD, dtype=torch.float32, device="cuda")
-    _lib.check(lib.tedspad_nl_attention_fwd(th.data_ptr(), d, pp, ldp, gp, ldg, out0.data_ptr(), ldo, n, q, k, d, scale, code, sp), "fwd")
-    _lib.check(lib.tedspad_nl_attention_fwd_lse(th.data_ptr(), d, pp, ldp, gp, ldg, out1.data_ptr(), ldo, lse.data_ptr(), n, q, k, d, scale, code, sp), "fwd_lse")
-    if sliced:
-        dpg = buf(n * k, 2 * d + 8)
-        dpp, dgp, lddp, lddg = dpg.data_ptr(), dpg.data_ptr() + 2 * d, 2 * d + 8, 2 * d + 8
+        ldp, ldg = L["phi"], L["g"]
+        (ph, pp), (gg, gp) = source(n * k, ldp, (phi, 0)), source(n * k, ldg, (g, 0))
+    ldo = L["t"]
+    (out0, o0p), (out1, o1p), (dth, dthp) = sink(n * q, ldo), sink(n * q, ldo), sink(n * q, L["dtheta"])
+    lse = floats()
+    lsep = lse.data_ptr() + 4 * G
+    _lib.check(lib.tedspad_nl_attention_fwd(thp, L["theta"], pp, ldp, gp, ldg, o0p, ldo, n, q, k, d, scale, code, sp), "fwd")
+    _lib.check(lib.tedspad_nl_attention_fwd_lse(thp, L["theta"], pp, ldp, gp, ldg, o1p, ldo, lsep, n, q, k, d, scale, code, sp), "fwd_lse")
+    if "dpg" in L:
+        lddp = lddg = L["dpg"][0]
+        dpg, dpp = sink(n * k, lddp)
+        dgp = dpp + 2 * L["dpg"][1]
     else:
-        dph, dgg = buf(n * k, ldo), buf(n * k, ldo)
-        dpp, dgp, lddp, lddg = dph.data_ptr(), dgg.data_ptr(), ldo, ldo
+        lddp, lddg = L["dphi"], L["dg"]
+        (dph, dpp), (dgg, dgp) = sink(n * k, lddp), sink(n * k, lddg)
     nbytes = C.c_int64(0)
     _lib.check(lib.tedspad_nl_attention_bwd_workspace(n, q, C.byref(nbytes)), "workspace")
     assert nbytes.value == n * q * 4
-    ws = torch.full((n * q + GUARD_ROWS,), LSE_GUARD, dtype=torch.float32, device="cuda")
-    _lib.check(lib.tedspad_nl_attention_bwd(th.data_ptr(), d, pp, ldp, gp, ldg, out1.data_ptr(), ldo, dtd.data_ptr(), d, lse.data_ptr(), dth.data_ptr(), ldo,
-                                            dpp, lddp, dgp, lddg, ws.data_ptr(), n, q, k, d, scale, code, sp), "bwd")
+    ws = floats()
+    tp, lsein = o1p, lsep                                  # as the training path does: the forward's own T and lse
+    if tape is not None or poison:
+        if tape is not None:
+            tin, tp = source(n * q, ldo, (tape[0].view(tdt).reshape(n, q, d), 0))
+            lse_rows = tape[1].reshape(-1).float().cuda()
+        else:                                              # the forward's results, with everything around them poisoned
+            torch.cuda.synchronize()
+            tin, tp = source(n * q, ldo)
+            tin[G:G + n * q, :d] = out1[G:G + n * q, :d]
+            lse_rows = lse[G:G + n * q]
+        lin = torch.full((n * q + 2 * G,), float("nan") if poison else LSE_GUARD, dtype=torch.float32, device="cuda")
+        lin[G:G + n * q] = lse_rows
+        lsein = lin.data_ptr() + 4 * G
+    _lib.check(lib.tedspad_nl_attention_bwd(thp, L["theta"], pp, ldp, gp, ldg, tp, ldo, dtp, L["dt"], lsein, dthp, L["dtheta"],
+                                            dpp, lddp, dgp, lddg, ws.data_ptr() + 4 * G, n, q, k, d, scale, code, sp), "bwd")
     torch.cuda.synchronize()
 
-    def image(t, rows, c0=0, width=None):
+    def image(t, rows, c0=0, others=()):
         host = t.cpu()
-        width = d if width is None else width
-        assert bool((host[rows:] == SENTINEL).all()), "guard rows behind an output were written"
-        assert bool((host[:rows, c0 + width:] == SENTINEL).all()), "the padding of an output row was written"
-        return host[:rows, c0:c0 + d].contiguous()
+        assert bool((host[:G] == SENTINEL).all()) and bool((host[G + rows:] == SENTINEL).all()), "guard rows around an output were written"
+        free = torch.ones(host.shape[1], dtype=torch.bool)
+        for c in (c0,) + tuple(others):
+            free[c:c + d] = False
+        assert bool((host[G:G + rows, free] == SENTINEL).all()), "the padding of an output row was written"
+        return host[G:G + rows, c0:c0 + d].contiguous()
     r = {"t0": image(out0, n * q), "t": image(out1, n * q), "dtheta": image(dth, n * q)}
-    if sliced:
-        r["dphi"], r["dg"] = image(dpg, n * k, 0, 2 * d), image(dpg, n * k, d, d)
+    if "dpg" in L:
+        off = L["dpg"][1]
+        r["dphi"], r["dg"] = image(dpg, n * k, 0, (off,)), image(dpg, n * k, off, (0,))
     else:
         r["dphi"], r["dg"] = image(dph, n * k), image(dgg, n * k)
     for t in (lse, ws):
-        assert bool((t[n * q:] == LSE_GUARD).all().cpu()), "guard floats behind lse / the workspace were written"
-    r["lse"] = lse[:n * q].cpu().double().reshape(n, q)
+        host = t.cpu()
+        assert bool((host[:G] == LSE_GUARD).all()) and bool((host[G + n * q:] == LSE_GUARD).all()), "guard floats around lse / the workspace were written"
+    r["lse"] = lse[G:G + n * q].cpu().double().reshape(n, q)
     for key in ("t", "dtheta", "dphi", "dg"):
         r[key + "64"] = r[key].view(tdt).double().reshape(n, -1, d)
     return r
+
+
+def lse_bound(ref_lse):
+    """|lse - ref| <= 2^-15 + 2^-20 |ref| (the header)."""
+    return 2.0 ** -15 + 2.0 ** -20 * ref_lse.abs()
+
+
+def dg_bound(ref, dt, dtype):
+    """|dg - ref| <= 2 u (P^T|dT| + |dg|), from the float64 reference alone (the header)."""
+    return 2.0 * U[dtype] * (torch.einsum("nqk,nqd->nkd", ref["p"], dt.double().abs()) + ref["dg"].abs())
 
 
 @functools.lru_cache(maxsize=None)
@@ -121,7 +185,7 @@ def test_fwd_lse_out_is_bit_equal_and_lse_within_its_bound(name, dtype):
     r, ref, _ = result(name, "plain", dtype)
     assert torch.equal(r["t"], r["t0"])
     err = (r["lse"] - ref["lse"]).abs()
-    bound = 2.0 ** -15 + 2.0 ** -20 * ref["lse"].abs()
+    bound = lse_bound(ref["lse"])
     print("%s %s: max |lse err| / bound = %.3f" % (name, dtype, float((err / bound).max())))
     assert bool((err <= bound).all())
 
@@ -175,7 +239,7 @@ def test_equal_logits_are_exact(dtype):
 @pytest.mark.parametrize("name", GENERAL)
 def test_dg_within_the_derived_bound(name, dtype):
     r, ref, dt = result(name, "plain", dtype)
-    bound = 2.0 * U[dtype] * (torch.einsum("nqk,nqd->nkd", ref["p"], dt.double().abs()) + ref["dg"].abs())
+    bound = dg_bound(ref, dt, dtype)
     err = (r["dg64"] - ref["dg"]).abs()
     print("%s %s: max |dg err| / bound = %.3f; bound / rms(dg) = %.4f" % (name, dtype, float((err / bound.clamp_min(1e-30)).max()),
                                                                         float(bound.mean() / ref["dg"].pow(2).mean().sqrt())))
@@ -211,7 +275,7 @@ def test_hard_inputs(name, variant, dtype):
             assert torch.equal(alone[key], r[key][b * rows:(b + 1) * rows]), key
         assert torch.equal(alone["lse"][0], r["lse"][b])
     else:
-        bound = 2.0 * U[dtype] * (torch.einsum("nqk,nqd->nkd", ref["p"], dt.double().abs()) + ref["dg"].abs())
+        bound = dg_bound(ref, dt, dtype)
         assert bool(((r["dg64"] - ref["dg"]).abs() <= bound).all())
 
 
