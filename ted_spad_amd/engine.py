@@ -88,6 +88,22 @@ def batch_chunk(n: int, per_sample_sizes, limit: int) -> int:
     return max(1, min(n, limit // worst))
 
 
+def sample_chunks(n: int, per_sample_sizes, limit: int, *more):
+    """The batch as ranges (n0, n1) of whole samples, each small enough for `batch_chunk(n, per_sample_sizes, limit)` -- and for every further
+    (sizes, limit) pair in `more`. A batch that fits one launch comes back as (0, n) alone, for which `Act.samples` is the Act itself. Callers pass
+    the limit they read from this module when they call (MAX_ELEMS, MAX_WGRAD_PIXELS): tests lower those."""
+    nc = batch_chunk(n, per_sample_sizes, limit)
+    for i in range(0, len(more), 2):
+        nc = min(nc, batch_chunk(n, more[i], more[i + 1]))
+    for first in range(0, n, nc):
+        yield first, min(n, first + nc)
+
+
+def dtype_code(t: torch.Tensor) -> int:
+    """The library's storage-type code of a 16-bit tensor."""
+    return _lib.F16 if t.dtype == torch.float16 else _lib.BF16
+
+
 class _Cfgs(dict):
     """geometry key -> chosen tile configuration (int) or the tuner's in-progress state (dict). One instance per convolution,
     SHARED by the PackedConv objects that succeed each other when the weights are re-packed after an optimizer step
@@ -185,6 +201,12 @@ class Act:
     def slice(self, coff: int, c: int) -> "Act":
         assert coff % 8 == 0 and c % 8 == 0 and coff + c <= self.c
         return Act(self.buf, c, self.coff + coff)
+
+    def samples(self, n0: int, n1: int) -> "Act":
+        """Samples [n0, n1) of the same channel view (a chunk of `sample_chunks`); the whole batch is this Act itself: nothing is sliced or re-wrapped."""
+        if n0 == 0 and n1 == self.buf.shape[0]:
+            return self
+        return Act(self.buf[n0:n1], self.c, self.coff, self.cpad)
 
     @staticmethod
     def empty(n, t, h, w, c, dtype, device) -> "Act":
@@ -558,10 +580,8 @@ class PackedConv:
             assert residual.dims == x.dims and residual.c == self.cout
         out = Act.empty(n, t // 2, h, w, self.cout, self.torch_dtype, x.buf.device)
         worst = max(t * h * w * x.ld, t * h * w * (residual.ld if residual is not None else self.cout))
-        nc = n if n * worst < MAX_ELEMS else batch_chunk(n, [worst], MAX_ELEMS)
-        for n0 in range(0, n, nc):
-            n1 = min(n, n0 + nc)
-            xs, rs, os_ = (Act(a.buf[n0:n1], a.c, a.coff) if a is not None else None for a in (x, residual, out))
+        for n0, n1 in sample_chunks(n, [worst], MAX_ELEMS):
+            xs, rs, os_ = (a.samples(n0, n1) if a is not None else None for a in (x, residual, out))
             d = self._desc(n1 - n0, t, h, w, xs.ld, (0, 0, 0), (t, h, w), os_.ld, rs.ld if rs is not None else 0, relu)
             check(_lib.lib().tedspad_conv_pool_t2_fwd(C.byref(d), xs.ptr, self.w.data_ptr(), self.scale.data_ptr(), self.shift.data_ptr(),
                                                       rs.ptr if rs is not None else None, os_.ptr, _stream_ptr()), "tedspad_conv_pool_t2_fwd")
@@ -578,10 +598,8 @@ class PackedConv:
         n, t, h, w = x.dims
         out = Act.empty(n, t, h, w, self.cout, self.torch_dtype, x.buf.device)
         worst = t * h * w * max(x.ld, x2.ld, self.cout)
-        nc = n if n * worst < MAX_ELEMS else batch_chunk(n, [worst], MAX_ELEMS)
-        for n0 in range(0, n, nc):
-            n1 = min(n, n0 + nc)
-            xs, x2s, os_ = (Act(a.buf[n0:n1], a.c, a.coff) for a in (x, x2, out))
+        for n0, n1 in sample_chunks(n, [worst], MAX_ELEMS):
+            xs, x2s, os_ = (a.samples(n0, n1) for a in (x, x2, out))
             d = self._desc(n1 - n0, t, h, w, xs.ld, (0, 0, 0), (t, h, w), os_.ld, 0, relu)
             check(_lib.lib().tedspad_conv_pw_dual_fwd(C.byref(d), xs.ptr, self.w.data_ptr(), self.scale.data_ptr(), self.shift.data_ptr(),
                                                       x2s.ptr, x2s.ld, other.w.data_ptr(), other.scale.data_ptr(), other.shift.data_ptr(),
@@ -675,12 +693,10 @@ class PackedConv:
             out = Act.empty(n, t, h, w, self.cout, self.torch_dtype, sources[0][0].buf.device)
         assert out.dims == (n, t, h, w) and out.c == self.cout
         worst = t * h * w * max(max(a.ld // (4 if up else 1) for a, up in sources), out.ld)
-        nc = n if n * worst < MAX_ELEMS else batch_chunk(n, [worst], MAX_ELEMS)
-        for n0 in range(0, n, nc):
-            n1 = min(n, n0 + nc)
-            sub = [(Act(a.buf[n0:n1], a.c, a.coff), up) for a, up in sources]
+        for n0, n1 in sample_chunks(n, [worst], MAX_ELEMS):
+            sub = [(a.samples(n0, n1), up) for a, up in sources]
             geo = _Geo((n1 - n0, t, h, w), self.cin)
-            self._run(geo, pads, o, Act(out.buf[n0:n1], out.c, out.coff), None, None, None, None, None, relu, False, sources=sub)
+            self._run(geo, pads, o, out.samples(n0, n1), None, None, None, None, None, relu, False, sources=sub)
         return out
 
     def __call__(self, x: Act, pads=(0, 0, 0), pads_back=None, out: Optional[Act] = None,
@@ -716,16 +732,10 @@ class PackedConv:
         od = out.dims
         worst = max(t * h * w * x.ld, od[1] * od[2] * od[3] * max(out.ld, self.cout if residual is None else residual.ld,
                                                                   0 if mask is None else mask.ld))
-        if n * worst < MAX_ELEMS:               # the common case: one launch
-            self._run(x, pads, o, out, residual, mask, stats, out_map, z32, relu, sigmoid)
-        else:
-            assert stats is None or stats.dim() == 2 or stats.shape[0] == 1, "grouped batch statistics: the batch must fit one launch"
-            nc = batch_chunk(n, [worst], MAX_ELEMS)
-            sub = lambda a, n0, n1: None if a is None else Act(a.buf[n0:n1], a.c, a.coff)
-            for n0 in range(0, n, nc):
-                n1 = min(n, n0 + nc)
-                self._run(sub(x, n0, n1), pads, o, sub(out, n0, n1), sub(residual, n0, n1), sub(mask, n0, n1), stats, out_map,
-                          None if z32 is None else z32[n0:n1], relu, sigmoid)
+        for n0, n1 in sample_chunks(n, [worst], MAX_ELEMS):               # the common case: one launch on the arguments as they are
+            assert n1 - n0 == n or stats is None or stats.dim() == 2 or stats.shape[0] == 1, "grouped batch statistics: the batch must fit one launch"
+            xs, os_, rs, ms = (a.samples(n0, n1) if a is not None else None for a in (x, out, residual, mask))
+            self._run(xs, pads, o, os_, rs, ms, stats, out_map, os_.buf if y32 else None, relu, sigmoid)
         return z32 if y32 else out
 
 
@@ -835,13 +845,13 @@ class BneckTail:
         return out
 
 
-class BneckTailFold:
-    """A plain layer1 block's BneckTail AND the next block's conv1 (3x1x1, pads (1,0,0), 256 -> 64) + bn1 + ReLU as ONE launch on four-frame clips
-    (csrc/conv_bneck_fold.hip; large_i3d.py:61-84): a workgroup owns an 8 x 8 patch (a partial one at the frame's right / bottom edge: layer1 is 55 x 55 at
-    224 x 224 clips) across the four frames, one frame per wave, so the temporal neighbours
-    of a pixel sit in sibling waves and the 256-channel block output is not read again only to make the next block's 64-channel h.
-    Returns (y, h_next); y is bit-identical to the BneckTail's. The two-source (downsample) tail has its own folded form, BneckTailFoldDual: this class
-    refuses it (`supported`)."""
+class _BneckFold:
+    """What the two folded layer1 tails share: a BneckTail AND the next block's conv1 (3x1x1, pads (1,0,0), 256 -> 64) + bn1 + ReLU as ONE launch on
+    four-frame clips (large_i3d.py:61-84). A workgroup owns an 8 x 8 patch (a partial one at the frame's right / bottom edge: layer1 is 55 x 55 at
+    224 x 224 clips) across the four frames, one frame per wave, so the temporal neighbours of a pixel sit in sibling waves and the 256-channel block
+    output is not read again only to make the next block's 64-channel h. Held here: the conv1 weight image, the output allocation, the checks and the
+    argument lists around the tail's second source. A subclass says which tail it takes (`supported`), which switches it obeys (`applies`) and which
+    entry point gets which second source (`__call__`); it returns (y, h_next), y bit-identical to its BneckTail's."""
 
     def __init__(self, tail: "BneckTail", conv1: "PackedConv", w1: torch.Tensor):
         """conv1: the next block's PackedConv (its folded scale / shift are used); w1: that conv's (64, 256, 3, 1, 1) weight."""
@@ -853,74 +863,64 @@ class BneckTailFold:
         self.w1p = w.to(tail.conv2.torch_dtype).contiguous()
 
     @staticmethod
-    def supported(tail: "BneckTail", w1: torch.Tensor) -> bool:
-        return (tuple(w1.shape) == (64, 256, 3, 1, 1) and tail.cmid == 64 and tail.cout3 == 256 and not tail.dual and tail.conv2.k == (1, 3, 3))
+    def _foldable(tail: "BneckTail", w1: torch.Tensor) -> bool:
+        return tuple(w1.shape) == (64, 256, 3, 1, 1) and tail.cmid == 64 and tail.cout3 == 256 and tail.conv2.k == (1, 3, 3)
 
-    def applies(self, x: Act, pads, residual: Optional[Act] = None) -> bool:
+    def _applies(self, x: Act, pads, src: Optional[Act]) -> bool:
         n, t, h, w = x.dims
-        return (L1_FOLD and t == 4 and tuple(pads) == (0, 1, 1) and x.buf.dtype == self.tail.conv2.torch_dtype == self.conv1.torch_dtype and
-                (residual is None or residual.buf.dtype == x.buf.dtype) and self.tail.applies(x, pads))
+        return (t == 4 and tuple(pads) == (0, 1, 1) and x.buf.dtype == self.tail.conv2.torch_dtype == self.conv1.torch_dtype and
+                (src is None or src.buf.dtype == x.buf.dtype) and self.tail.applies(x, pads))
 
-    def __call__(self, x: Act, residual: Act, pads=(0, 1, 1), relu=True, out: Optional[Act] = None, out_h: Optional[Act] = None):
+    def _args(self, x: Act, src: Act, src_c: int, pads, relu, out: Optional[Act], out_h: Optional[Act]):
+        """(out, out_h, the entry point's arguments in front of the second source, those behind it); src: the second source, of src_c channels."""
         n, t, h, w = x.dims
         tl, c2 = self.tail, self.tail.conv2
-        assert self.applies(x, pads, residual) and residual.dims == x.dims and residual.c == 256
+        assert self.applies(x, pads, src) and src.dims == x.dims and src.c == src_c
         if out is None:
             out = Act.empty(n, t, h, w, 256, c2.torch_dtype, x.buf.device)
         if out_h is None:
             out_h = Act.empty(n, t, h, w, 64, c2.torch_dtype, x.buf.device)
         assert out.dims == x.dims and out.c == 256 and out_h.dims == x.dims and out_h.c == 64
-        assert n * t * h * w * max(x.ld, out.ld, out_h.ld, residual.ld) < MAX_ELEMS
+        assert n * t * h * w * max(x.ld, out.ld, out_h.ld, src.ld) < MAX_ELEMS
         d = c2._desc(n, t, h, w, x.ld, pads, (t, h, w), 64, 0, True)
-        check(_lib.lib().tedspad_bneck_tail_fold_fwd(C.byref(d), x.ptr, c2.w.data_ptr(), c2.scale.data_ptr(), c2.shift.data_ptr(), tl.w3p.data_ptr(),
-                                                     tl.scale3.data_ptr(), tl.shift3.data_ptr(), residual.ptr, residual.ld, out.ptr, out.ld, int(relu),
-                                                     self.w1p.data_ptr(), self.conv1.scale.data_ptr(), self.conv1.shift.data_ptr(), out_h.ptr, out_h.ld,
-                                                     _stream_ptr()),
-              "tedspad_bneck_tail_fold_fwd")
-        return out, out_h
+        front = (C.byref(d), x.ptr, c2.w.data_ptr(), c2.scale.data_ptr(), c2.shift.data_ptr(), tl.w3p.data_ptr(), tl.scale3.data_ptr(), tl.shift3.data_ptr())
+        back = (out.ptr, out.ld, int(relu), self.w1p.data_ptr(), self.conv1.scale.data_ptr(), self.conv1.shift.data_ptr(), out_h.ptr, out_h.ld, _stream_ptr())
+        return out, out_h, front, back
 
 
-class BneckTailFoldDual:
-    """layer1.0's two-source BneckTail (conv3 + bn3 + the downsample branch on x2) AND layer1.1's conv1 (3x1x1, pads (1,0,0), 256 -> 64) + bn1 + ReLU as ONE
-    launch on four-frame clips (csrc/conv_bneck_fold_dual.hip): BneckTailFold's tile and fold with the downsample branch in place of the residual. The wave's
-    LDS row image holds its frame's 64 channels of x2, fetched again for each of the four output groups (L2 hits), so the second source costs no registers
-    beside the fold's tile. Reuses the tail's w3p / scale3 / shift3 / scale_d and BneckTailFold's w1p layout. Returns (y, h_next); y is bit-identical to
-    the two-source BneckTail's. Runs when both TEDSPAD_L1_FOLD and TEDSPAD_L1_FOLD_DUAL are on."""
-
-    def __init__(self, tail: "BneckTail", conv1: "PackedConv", w1: torch.Tensor):
-        """conv1: the next block's PackedConv (its folded scale / shift are used); w1: that conv's (64, 256, 3, 1, 1) weight."""
-        assert self.supported(tail, w1)
-        dev = tail.conv2.device
-        self.tail, self.conv1 = tail, conv1
-        w = w1.detach().to(dev, torch.float32).reshape(64, 4, 64, 3).permute(1, 3, 0, 2).contiguous()      # [group][dt][co][k], as BneckTailFold's
-        w[:, 1] = w[:, 1][:, :, torch.tensor(BneckTail.PERM[:64], device=dev)]                                # dt = 0 tap: accumulator k order
-        self.w1p = w.to(tail.conv2.torch_dtype).contiguous()
+class BneckTailFold(_BneckFold):
+    """A plain layer1 block's BneckTail and the next block's conv1 (csrc/conv_bneck_fold.hip). The two-source (downsample) tail has its own folded form,
+    BneckTailFoldDual: this class refuses it (`supported`)."""
 
     @staticmethod
     def supported(tail: "BneckTail", w1: torch.Tensor) -> bool:
-        return (tuple(w1.shape) == (64, 256, 3, 1, 1) and tail.cmid == 64 and tail.cout3 == 256 and tail.dual and tail.conv2.k == (1, 3, 3))
+        return _BneckFold._foldable(tail, w1) and not tail.dual
+
+    def applies(self, x: Act, pads, residual: Optional[Act] = None) -> bool:
+        return L1_FOLD and self._applies(x, pads, residual)
+
+    def __call__(self, x: Act, residual: Act, pads=(0, 1, 1), relu=True, out: Optional[Act] = None, out_h: Optional[Act] = None):
+        out, out_h, front, back = self._args(x, residual, 256, pads, relu, out, out_h)
+        check(_lib.lib().tedspad_bneck_tail_fold_fwd(*front, residual.ptr, residual.ld, *back), "tedspad_bneck_tail_fold_fwd")
+        return out, out_h
+
+
+class BneckTailFoldDual(_BneckFold):
+    """layer1.0's two-source BneckTail (conv3 + bn3 + the downsample branch on x2) and layer1.1's conv1 (csrc/conv_bneck_fold_dual.hip): BneckTailFold's
+    tile and fold with the downsample branch in place of the residual. The wave's LDS row image holds its frame's 64 channels of x2, fetched again for
+    each of the four output groups (L2 hits), so the second source costs no registers beside the fold's tile. Reuses the tail's w3p / scale3 / shift3 /
+    scale_d. Runs when both TEDSPAD_L1_FOLD and TEDSPAD_L1_FOLD_DUAL are on."""
+
+    @staticmethod
+    def supported(tail: "BneckTail", w1: torch.Tensor) -> bool:
+        return _BneckFold._foldable(tail, w1) and tail.dual
 
     def applies(self, x: Act, pads, x2: Optional[Act] = None) -> bool:
-        n, t, h, w = x.dims
-        return (L1_FOLD and L1_FOLD_DUAL and t == 4 and tuple(pads) == (0, 1, 1) and x.buf.dtype == self.tail.conv2.torch_dtype == self.conv1.torch_dtype and
-                (x2 is None or x2.buf.dtype == x.buf.dtype) and self.tail.applies(x, pads))
+        return L1_FOLD and L1_FOLD_DUAL and self._applies(x, pads, x2)
 
     def __call__(self, x: Act, x2: Act, pads=(0, 1, 1), relu=True, out: Optional[Act] = None, out_h: Optional[Act] = None):
-        n, t, h, w = x.dims
-        tl, c2 = self.tail, self.tail.conv2
-        assert self.applies(x, pads, x2) and x2.dims == x.dims and x2.c == 64
-        if out is None:
-            out = Act.empty(n, t, h, w, 256, c2.torch_dtype, x.buf.device)
-        if out_h is None:
-            out_h = Act.empty(n, t, h, w, 64, c2.torch_dtype, x.buf.device)
-        assert out.dims == x.dims and out.c == 256 and out_h.dims == x.dims and out_h.c == 64
-        assert n * t * h * w * max(x.ld, out.ld, out_h.ld, x2.ld) < MAX_ELEMS
-        d = c2._desc(n, t, h, w, x.ld, pads, (t, h, w), 64, 0, True)
-        check(_lib.lib().tedspad_bneck_tail_fold2_fwd(C.byref(d), x.ptr, c2.w.data_ptr(), c2.scale.data_ptr(), c2.shift.data_ptr(), tl.w3p.data_ptr(),
-                                                      tl.scale3.data_ptr(), tl.shift3.data_ptr(), x2.ptr, x2.ld, tl.scale_d.data_ptr(), out.ptr, out.ld,
-                                                      int(relu), self.w1p.data_ptr(), self.conv1.scale.data_ptr(), self.conv1.shift.data_ptr(), out_h.ptr,
-                                                      out_h.ld, _stream_ptr()),
-              "tedspad_bneck_tail_fold2_fwd")
+        out, out_h, front, back = self._args(x, x2, 64, pads, relu, out, out_h)
+        check(_lib.lib().tedspad_bneck_tail_fold2_fwd(*front, x2.ptr, x2.ld, self.tail.scale_d.data_ptr(), *back), "tedspad_bneck_tail_fold2_fwd")
         return out, out_h
 
 
@@ -997,7 +997,7 @@ def maxpool(x: Act, k, s, pads=(0, 0, 0), pads_back=None, pad_zero=False, out: O
     o = tuple(conv_out(sz, kk, ss, pf, pbk) for sz, kk, ss, pf, pbk in zip((t, h, w), k, s, pads, pb))
     if out is None:
         out = Act.empty(n, o[0], o[1], o[2], x.c, x.buf.dtype, x.buf.device)
-    code = _lib.F16 if x.buf.dtype == torch.float16 else _lib.BF16
+    code = dtype_code(x.buf)
     d = PoolDesc(n=n, t=t, h=h, w=w, c=x.c, ldx=x.ld, ldy=out.ld, kt=k[0], kh=k[1], kw=k[2], st=s[0], sh=s[1], sw=s[2],
                  pt=pads[0], ph=pads[1], pw=pads[2], to=o[0], ho=o[1], wo=o[2], pad_zero=int(pad_zero), dtype=code)
     idx = torch.empty((n, o[0], o[1], o[2], x.c), dtype=torch.uint8, device=x.buf.device) if return_idx else None
@@ -1020,17 +1020,15 @@ def nl_attention(theta: Act, phi: Act, g: Act, scale: float, out: Optional[Act] 
         out = Act.empty(n, t, h, w, theta.c, theta.buf.dtype, theta.buf.device)
     assert out.dims == theta.dims and out.c == theta.c and out.buf.dtype == theta.buf.dtype
     q, k = t * h * w, phi.dims[1] * phi.dims[2] * phi.dims[3]
-    code = _lib.F16 if theta.buf.dtype == torch.float16 else _lib.BF16
-    nc = batch_chunk(n, [q * max(theta.ld, out.ld), k * max(phi.ld, g.ld)], MAX_ELEMS)
-    for n0 in range(0, n, nc):
-        n1 = min(n, n0 + nc)
-        ts, ps, gs, os_ = (Act(a.buf[n0:n1], a.c, a.coff) for a in (theta, phi, g, out))
+    code = dtype_code(theta.buf)
+    assert lse is None or (lse.dtype == torch.float32 and lse.is_contiguous() and tuple(lse.shape) == (n, q))
+    for n0, n1 in sample_chunks(n, [q * max(theta.ld, out.ld), k * max(phi.ld, g.ld)], MAX_ELEMS):
+        ts, ps, gs, os_ = (a.samples(n0, n1) for a in (theta, phi, g, out))
         if lse is None:
             check(_lib.lib().tedspad_nl_attention_fwd(ts.ptr, ts.ld, ps.ptr, ps.ld, gs.ptr, gs.ld, os_.ptr, os_.ld, n1 - n0, q, k, theta.c, C.c_float(scale), code,
                                                       _stream_ptr()), "tedspad_nl_attention_fwd")
-        else:
-            assert lse.dtype == torch.float32 and lse.is_contiguous() and tuple(lse.shape) == (n, q)
-            check(_lib.lib().tedspad_nl_attention_fwd_lse(ts.ptr, ts.ld, ps.ptr, ps.ld, gs.ptr, gs.ld, os_.ptr, os_.ld, lse[n0:n1].data_ptr(), n1 - n0, q, k,
+        else:                                               # row n0 of the contiguous (n, q) fp32 tensor
+            check(_lib.lib().tedspad_nl_attention_fwd_lse(ts.ptr, ts.ld, ps.ptr, ps.ld, gs.ptr, gs.ld, os_.ptr, os_.ld, lse.data_ptr() + 4 * q * n0, n1 - n0, q, k,
                                                           theta.c, C.c_float(scale), code, _stream_ptr()), "tedspad_nl_attention_fwd_lse")
     return out
 
@@ -1052,19 +1050,17 @@ def nl_attention_bwd(theta: Act, phi: Act, g: Act, t: Act, lse: torch.Tensor, dt
     q, k = tt * h * w, phi.dims[1] * phi.dims[2] * phi.dims[3]
     assert lse.dtype == torch.float32 and lse.is_contiguous() and tuple(lse.shape) == (n, q)
     tdt, dev = theta.buf.dtype, theta.buf.device
-    code = _lib.F16 if tdt == torch.float16 else _lib.BF16
+    code = dtype_code(theta.buf)
     dtheta = Act.empty(n, tt, h, w, d, tdt, dev)
     dphi, dg = Act.empty(*phi.dims, d, tdt, dev), Act.empty(*phi.dims, d, tdt, dev)
     nbytes = C.c_int64(0)
     check(_lib.lib().tedspad_nl_attention_bwd_workspace(n, q, C.byref(nbytes)), "tedspad_nl_attention_bwd_workspace")
     ws = torch.empty(nbytes.value // 4, dtype=torch.float32, device=dev)
     acts = (theta, phi, g, t, dt, dtheta, dphi, dg)
-    nc = batch_chunk(n, [q * max(a.ld for a in (theta, t, dt, dtheta)), k * max(a.ld for a in (phi, g, dphi, dg))], MAX_ELEMS)
-    for n0 in range(0, n, nc):
-        n1 = min(n, n0 + nc)
-        s = [Act(a.buf[n0:n1], a.c, a.coff) for a in acts]
+    for n0, n1 in sample_chunks(n, [q * max(a.ld for a in (theta, t, dt, dtheta)), k * max(a.ld for a in (phi, g, dphi, dg))], MAX_ELEMS):
+        s = [a.samples(n0, n1) for a in acts]
         check(_lib.lib().tedspad_nl_attention_bwd(s[0].ptr, s[0].ld, s[1].ptr, s[1].ld, s[2].ptr, s[2].ld, s[3].ptr, s[3].ld, s[4].ptr, s[4].ld,
-                                                  lse[n0:n1].data_ptr(), s[5].ptr, s[5].ld, s[6].ptr, s[6].ld, s[7].ptr, s[7].ld, ws.data_ptr(), n1 - n0, q, k, d,
+                                                  lse.data_ptr() + 4 * q * n0, s[5].ptr, s[5].ld, s[6].ptr, s[6].ld, s[7].ptr, s[7].ld, ws.data_ptr(), n1 - n0, q, k, d,
                                                   C.c_float(scale), code, _stream_ptr()), "tedspad_nl_attention_bwd")
     return dtheta, dphi, dg
 
@@ -1073,7 +1069,7 @@ def global_avgpool(x: Act) -> torch.Tensor:
     """(n,t,h,w,c) -> fp32 (n, c): mean over all pixels."""
     n, t, h, w = x.dims
     y = torch.empty((n, x.c), dtype=torch.float32, device=x.buf.device)
-    code = _lib.F16 if x.buf.dtype == torch.float16 else _lib.BF16
+    code = dtype_code(x.buf)
     check(_lib.lib().tedspad_global_avgpool_fwd(x.ptr, y.data_ptr(), n, t * h * w, x.c, x.ld, code, _stream_ptr()),
           "tedspad_global_avgpool_fwd")
     return y
@@ -1085,7 +1081,7 @@ def count_saturated(x: Act, counter: Optional[torch.Tensor] = None) -> torch.Ten
     if counter is None:
         counter = torch.zeros(2, dtype=torch.int32, device=x.buf.device)
     n, t, h, w = x.dims
-    code = _lib.F16 if x.buf.dtype == torch.float16 else _lib.BF16
+    code = dtype_code(x.buf)
     check(_lib.lib().tedspad_count_saturated(x.ptr, n * t * h * w, x.c, x.ld, code, counter.data_ptr(), _stream_ptr()), "tedspad_count_saturated")
     return counter
 
@@ -1094,7 +1090,7 @@ def avgpool3d_stride1(x: Act, k) -> torch.Tensor:
     """nn.AvgPool3d(k, stride 1): (n,t,h,w,c) -> fp32 (n, c, t-kt+1, h-kh+1, w-kw+1)."""
     n, t, h, w = x.dims
     y = torch.empty((n, x.c, t - k[0] + 1, h - k[1] + 1, w - k[2] + 1), dtype=torch.float32, device=x.buf.device)
-    code = _lib.F16 if x.buf.dtype == torch.float16 else _lib.BF16
+    code = dtype_code(x.buf)
     check(_lib.lib().tedspad_avgpool3d_s1_fwd(x.ptr, y.data_ptr(), n, t, h, w, x.c, x.ld, k[0], k[1], k[2], code, _stream_ptr()),
           "tedspad_avgpool3d_s1_fwd")
     return y
@@ -1244,7 +1240,7 @@ def act_to_nchw(x: Act, c: Optional[int] = None) -> torch.Tensor:
     n, t, h, w = x.dims
     c = x.c if c is None else c
     y = torch.empty((n, c, t, h, w), dtype=torch.float32, device=x.buf.device)
-    code = _lib.F16 if x.buf.dtype == torch.float16 else _lib.BF16
+    code = dtype_code(x.buf)
     check(_lib.lib().tedspad_channels_last_to_nchw(x.ptr, y.data_ptr(), n, c, t, h, w, x.ld, code, _stream_ptr()),
           "tedspad_channels_last_to_nchw")
     return y
@@ -1255,7 +1251,7 @@ def upsample2x_into(x: Act, out: Act, pad_top=0, pad_left=0):
     n, t, h, w = x.dims
     no, to, ho, wo = out.dims
     assert t == 1 and to == 1 and no == n and out.c == x.c
-    code = _lib.F16 if x.buf.dtype == torch.float16 else _lib.BF16
+    code = dtype_code(x.buf)
     check(_lib.lib().tedspad_upsample_bilinear2x_fwd(x.ptr, out.ptr, n, h, w, x.c, x.ld, out.ld, ho, wo, pad_top, pad_left,
                                                      code, _stream_ptr()), "tedspad_upsample_bilinear2x_fwd")
     return out

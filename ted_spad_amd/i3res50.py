@@ -133,38 +133,7 @@ class I3Res50(nn.Module):
             P["stem_pt"] = E.StemPT(self.conv1.weight, s, b, stride=(2, 2, 2), pads=(2, 3, 3), dtype=self.compute_dtype, device=dev)
             for li in range(1, 5):
                 for i, blk in enumerate(getattr(self, "layer%d" % li)):
-                    p = "layer%d.%d." % (li, i)
-                    s, b = self._bn_fold(blk.bn1)
-                    P[p + "conv1"] = E.PackedConv(blk.conv1.weight, s, b, dtype=self.compute_dtype, device=dev)
-                    if li >= 2 and blk.temp_conv and E.TPairConv.supported(blk.conv1.weight):      # layers behind maxpool2: T = 2 at 16-frame clips
-                        P[p + "conv1_tp"] = E.TPairConv(blk.conv1.weight, s, b, dtype=self.compute_dtype, device=dev)
-                    s, b = self._bn_fold(blk.bn2)
-                    P[p + "conv2"] = E.PackedConv(blk.conv2.weight, s, b, stride=(1, blk.stride, blk.stride),
-                                                  dtype=self.compute_dtype, device=dev)
-                    s, b = self._bn_fold(blk.bn3)
-                    P[p + "conv3"] = E.PackedConv(blk.conv3.weight, s, b, dtype=self.compute_dtype, device=dev)
-                    if blk.downsample is not None:
-                        s, b = self._bn_fold(blk.downsample[1])
-                        P[p + "down"] = E.PackedConv(blk.downsample[0].weight, s, b, stride=(1, blk.stride, blk.stride),
-                                                     dtype=self.compute_dtype, device=dev)
-                    if blk.downsample is None and E.BneckFrame.supported(blk.conv1.weight, blk.conv2.weight, blk.conv3.weight):
-                        # layer3's plain blocks: the whole bottleneck in one launch, a workgroup per 14 x 14 frame
-                        P[p + "frame"] = E.BneckFrame(blk.conv1.weight, *self._bn_fold(blk.bn1), blk.conv2.weight, *self._bn_fold(blk.bn2),
-                                                      blk.conv3.weight, *self._bn_fold(blk.bn3), dtype=self.compute_dtype, device=dev)
-                    if li in (1, 2) and E.BneckTail.supported(P[p + "conv2"], blk.conv3.weight, blk.downsample[0].weight if blk.downsample is not None else None):
-                        s3, b3 = self._bn_fold(blk.bn3)
-                        if blk.downsample is not None and blk.stride == 1:
-                            sd_, bd_ = self._bn_fold(blk.downsample[1])
-                            P[p + "tail"] = E.BneckTail(P[p + "conv2"], blk.conv3.weight, s3, b3, blk.downsample[0].weight, sd_, bd_)
-                        elif blk.downsample is None:
-                            P[p + "tail"] = E.BneckTail(P[p + "conv2"], blk.conv3.weight, s3, b3)
-                    if blk.downsample is not None:
-                        if blk.stride == 2:     # conv3 + bn3 and the strided downsample branch as one K-concatenated GEMM
-                            s3, b3 = self._bn_fold(blk.bn3)
-                            P[p + "dual"] = E.PackedConv.fused_pair(blk.conv3.weight, s3, b3, blk.downsample[0].weight, s, b,
-                                                                    dtype=self.compute_dtype, device=dev)
-                    if blk.nl is not None:
-                        pack_nonlocal(P, p + "nl.", blk.nl, self.compute_dtype, dev)
+                    self._pack_block(P, "layer%d.%d." % (li, i), li, blk, dev)
             for i in range(len(self.layer1) - 1):               # a plain layer1 tail that also emits the next block's conv1 (four-frame clips)
                 p, q = "layer1.%d." % i, "layer1.%d." % (i + 1)
                 w1 = self.layer1[i + 1].conv1.weight
@@ -174,6 +143,36 @@ class I3Res50(nn.Module):
                     P[p + "fold2"] = E.BneckTailFoldDual(P[p + "tail"], P[q + "conv1"], w1)
             self._packed, self._packed_sig = P, sig
         return self._packed
+
+    def _pack_block(self, P: dict, p: str, li: int, blk: Bottleneck, dev) -> None:
+        """The images of one bottleneck of layer `li` into `P` under prefix `p`. Every BatchNorm of the block is folded ONCE; the objects that need it
+        share that (scale, shift) read-only (PackedConv views the vectors, BneckFrame clones them)."""
+        dt = self.compute_dtype
+        w1, w2, w3 = blk.conv1.weight, blk.conv2.weight, blk.conv3.weight
+        wd = blk.downsample[0].weight if blk.downsample is not None else None
+        s1, b1 = self._bn_fold(blk.bn1)
+        s2, b2 = self._bn_fold(blk.bn2)
+        s3, b3 = self._bn_fold(blk.bn3)
+        P[p + "conv1"] = E.PackedConv(w1, s1, b1, dtype=dt, device=dev)
+        if li >= 2 and blk.temp_conv and E.TPairConv.supported(w1):      # layers behind maxpool2: T = 2 at 16-frame clips
+            P[p + "conv1_tp"] = E.TPairConv(w1, s1, b1, dtype=dt, device=dev)
+        P[p + "conv2"] = E.PackedConv(w2, s2, b2, stride=(1, blk.stride, blk.stride), dtype=dt, device=dev)
+        P[p + "conv3"] = E.PackedConv(w3, s3, b3, dtype=dt, device=dev)
+        if wd is not None:
+            sd, bd = self._bn_fold(blk.downsample[1])
+            P[p + "down"] = E.PackedConv(wd, sd, bd, stride=(1, blk.stride, blk.stride), dtype=dt, device=dev)
+        elif E.BneckFrame.supported(w1, w2, w3):
+            # layer3's plain blocks: the whole bottleneck in one launch, a workgroup per 14 x 14 frame
+            P[p + "frame"] = E.BneckFrame(w1, s1, b1, w2, s2, b2, w3, s3, b3, dtype=dt, device=dev)
+        if li in (1, 2) and E.BneckTail.supported(P[p + "conv2"], w3, wd):
+            if wd is None:
+                P[p + "tail"] = E.BneckTail(P[p + "conv2"], w3, s3, b3)
+            elif blk.stride == 1:
+                P[p + "tail"] = E.BneckTail(P[p + "conv2"], w3, s3, b3, wd, sd, bd)
+        if wd is not None and blk.stride == 2:      # conv3 + bn3 and the strided downsample branch as one K-concatenated GEMM
+            P[p + "dual"] = E.PackedConv.fused_pair(w3, s3, b3, wd, sd, bd, dtype=dt, device=dev)
+        if blk.nl is not None:
+            pack_nonlocal(P, p + "nl.", blk.nl, dt, dev)
 
     # ---- the launch sequence ---------------------------------------------------------------
     def _check_geometry(self, frames: int, h: int, w: int, shape) -> None:
@@ -199,50 +198,13 @@ class I3Res50(nn.Module):
 
     def _trunk(self, x: torch.Tensor, taps=None, records: torch.Tensor = None) -> E.Act:
         """conv1 .. layer4 (large_i3d.py:229-238 == :251-260) on a (B,3,T,H,W) fp32 clip batch -- or, with `records`, on the persistent stem's own 16-bit input
-        layout X[n][tp][h][2][w/2][24] (engine.StemPT.layout; preprocess.crop_resize_records writes it straight from uint8 frames)."""
+        layout X[n][tp][h][2][w/2][24] (engine.StemPT.layout; preprocess.crop_resize_records writes it straight from uint8 frames). `taps`: a dict that
+        receives the stage outputs; the network then runs its generic sequence, every convolution a launch of its own."""
         if self.training:
             raise NotImplementedError("a bare I3Res50 in train() mode has no caller in the reference: training goes through wrapper_i3d "
                                       "(load_ft_model('largei3d'); ted_spad_amd/autograd.py) or train_step.AnonymizerTrainStep")
         P = self.packed()
-        if records is not None:
-            E.require_cuda(records, "I3Res50")
-            if not (E.STEM_PT and E.STEM_POOL) or "stem_pt" not in P:
-                raise _lib.TedSpadHipError("I3Res50: the stem-record input needs the persistent stem with the fused pool (TEDSPAD_STEM_PT / TEDSPAD_STEM_POOL are off, "
-                                           "or this weight shape has no persistent stem): feed the (B,3,T,H,W) clip instead")
-            st = P["stem_pt"]
-            if records.dim() != 6 or tuple(records.shape[3:]) != (2, records.shape[4], 24) or records.dtype != st.torch_dtype or not records.is_contiguous():
-                raise ValueError("expected contiguous stem records (n, frame pairs, h, 2, w/2, 24) of %s, got %s %s" % (st.torch_dtype, tuple(records.shape), records.dtype))
-            if records.shape[1] < 1 or (records.shape[2] + 1) // 2 < 3 or records.shape[4] < 3:
-                raise ValueError("stem records need at least one frame pair and frames of 5 x 6 pixels for conv1 + maxpool1, got %s" % (tuple(records.shape),))
-            self._check_geometry(int(records.shape[1]), int(records.shape[2]), 2 * int(records.shape[4]), tuple(records.shape))
-            a = st.conv_pool(records)                                    # conv1 + bn1 + ReLU + maxpool1 from the records (the LDS-DMA loader of csrc/conv_stem_pt.hip)
-            x = None
-        else:
-            E.require_cuda(x, "I3Res50")
-            if x.dim() != 5 or x.shape[1] != 3:
-                raise ValueError("expected (B,3,T,H,W), got %s" % (tuple(x.shape),))
-            if x.shape[4] % 2:
-                raise ValueError("W must be even")
-            self._check_geometry(E.conv_out(int(x.shape[2]), 5, 2, 2, 2) // 2, int(x.shape[3]), int(x.shape[4]), tuple(x.shape))
-        if records is not None:
-            pass
-        elif E.STEM_PT and taps is None and P["stem_pt"].applies(x):
-            # conv1 + bn1 + ReLU + maxpool1 on the persistent stem kernel (large_i3d.py:229-232): the 112 x 112 x 8-frame stem tensor
-            # is never written
-            st = P["stem_pt"]
-            if E.STEM_POOL and x.shape[3] >= 5 and x.shape[4] >= 6:
-                if E.STEM_CLIP and (st.VARIANT & 4) and st.direct_applies(x):
-                    a = st.conv_pool_clip(x)                             # ... straight from the fp32 NCTHW clip: no layout pass either
-                else:
-                    a = st.conv_pool(st.layout(x))                       # ... and the spatial half: only the pooled tensor is written
-            else:
-                a = E.maxpool(st(x), (1, 3, 3), (1, 2, 2))               # the spatial half of MaxPool3d((2,3,3), 2)
-        else:
-            a = E.clip_to_act(x, cpad=4, dtype=self.compute_dtype)       # (B,T,H,W/2, 2px x 4ch)
-            a = P["stem"](a, pads=(2, 3, P["stem"].pair_pw), pads_back=(2, 3, 1))   # the same conv in pixel-pair form, K = 5*7*4*8
-            if taps is not None:
-                taps["stem"] = a
-            a = E.maxpool(a, (2, 3, 3), (2, 2, 2))                       # large_i3d.py:138
+        a = self._stem(P, x, taps, records)
         if taps is not None:
             taps["maxpool1"] = a
         if self.check_saturation:
@@ -254,76 +216,97 @@ class I3Res50(nn.Module):
             layer = getattr(self, "layer%d" % li)
             for i, blk in enumerate(layer):
                 p = "layer%d.%d." % (li, i)
-                bf = P.get(p + "frame") if taps is None else None
-                if bf is not None and bf.applies(a):
-                    a = bf(a)                                             # conv1 -> conv2 -> conv3 + residual: only the block input and output touch HBM
-                    if blk.nl is not None:
-                        a = self._nonlocal(P, p, blk.nl, a, taps)
-                    continue
-                tp = P.get(p + "conv1_tp") if taps is None else None
-                if h_next is not None:
-                    h, h_next = h_next, None                              # conv1 + bn1 + ReLU came out of the previous block's tail (BneckTailFold)
-                elif tp is not None and tp.applies(a, (blk.temp_conv, 0, 0)):
-                    h = tp(a)                                             # two frames: both outputs from ONE K = 2*cin GEMM, no products on zero padding
-                else:
-                    h = P[p + "conv1"](a, pads=(blk.temp_conv, 0, 0))
-                tail = P.get(p + "tail") if (E.BNECK_TAIL and taps is None) else None
-                if tail is not None and tail.cmid == 128 and not E.BNECK_TAIL128:
-                    tail = None
-                fuse_pool = li == 1 and i == len(layer) - 1          # the last layer1 block fuses maxpool2 into its conv3 instead (below)
-                if tail is not None and tail.applies(h, (0, 1, 1)) and (not fuse_pool or (E.BNECK_TAIL_POOL and not tail.dual and h.dims[1] % 2 == 0)):
-                    # conv2 + bn2 + ReLU + conv3 + bn3 + (residual | downsample branch) + ReLU in one launch: the 64-channel tensor between
-                    # the two convolutions is never written (large_i3d.py:69-84); the last block of layer1 pools over frame pairs as
-                    # well (maxpool2, large_i3d.py:139)
-                    fold = P.get(p + "fold") if not fuse_pool else None
-                    fold2 = P.get(p + "fold2") if not fuse_pool else None
-                    if tail.dual and fold2 is not None and fold2.applies(h, (0, 1, 1), a):
-                        a, h_next = fold2(h, x2=a)                       # the downsample tail and the next block's conv1 + bn1 + ReLU (BneckTailFoldDual)
-                    elif tail.dual:
-                        a = tail(h, pads=(0, 1, 1), x2=a)
-                    elif fold is not None and fold.applies(h, (0, 1, 1), a):
-                        a, h_next = fold(h, residual=a)                  # ... and the next block's conv1 (3x1x1) + bn1 + ReLU: the block output is not read for it again
-                    else:
-                        a = tail(h, pads=(0, 1, 1), residual=a, pool_t2=fuse_pool)
-                        pooled = pooled or fuse_pool
-                    if blk.nl is not None:
-                        a = self._nonlocal(P, p, blk.nl, a, taps)
-                    continue
-                h = P[p + "conv2"](h, pads=(0, 1, 1))
-                if blk.downsample is not None and taps is None and P[p + "conv3"].dual_supported(P[p + "down"], h, a):
-                    # layer1.0: conv3 + bn3 and the downsample branch in one launch (the 256-channel downsample tensor
-                    # is never written; both branches stay fp32 until the sum)
-                    a = P[p + "conv3"].call_dual(h, P[p + "down"], a, relu=True)
-                    if blk.nl is not None:
-                        a = self._nonlocal(P, p, blk.nl, a, taps)
-                    continue
-                if (p + "dual") in P and taps is None and P[p + "dual"].dual_p8_supported(h, a, (blk.stride, blk.stride)):
-                    # layer2.0 / 3.0 / 4.0: the same pair as ONE GEMM over [W3*s3 | Wd*sd] on the ping-pong kernel
-                    a = P[p + "dual"].call_dual_p8(h, a, (blk.stride, blk.stride), relu=True)
-                    if blk.nl is not None:
-                        a = self._nonlocal(P, p, blk.nl, a, taps)
-                    continue
-                res = P[p + "down"](a, relu=False) if blk.downsample is not None else a
-                if li == 1 and i == len(layer) - 1 and taps is None and P[p + "conv3"].pool_t2_supported(h):
-                    # the block's tail and maxpool2 (large_i3d.py:139) in one launch: the 256-channel tensor is only
-                    # written after the temporal pooling (half the bytes, no separate pool pass)
-                    a = P[p + "conv3"].call_pool_t2(h, residual=res, relu=True)
-                    pooled = True
-                else:
-                    a = P[p + "conv3"](h, residual=res, relu=True)       # bn3 + (+= residual) + ReLU fused
+                # the last layer1 block may fuse maxpool2 into its tail or its conv3
+                a, h_next, fused_pool = self._bottleneck(P, p, blk, a, h_next, taps is None, li == 1 and i == len(layer) - 1)
+                pooled = pooled or fused_pool
                 if blk.nl is not None:
-                    a = self._nonlocal(P, p, blk.nl, a, taps)
+                    a = nonlocal_forward(P, p + "nl.", blk.nl, a)
+                    if taps is not None:
+                        taps[p + "nl"] = a
             if taps is not None:
                 taps["layer%d" % li] = a
             if self.check_saturation:
                 self._sat = E.count_saturated(a, self._sat)
         return a
 
-    def _nonlocal(self, P, p, nl, a: E.Act, taps=None) -> E.Act:
-        a = nonlocal_forward(P, p + "nl.", nl, a)
+    def _stem(self, P: dict, x: torch.Tensor, taps, records: torch.Tensor) -> E.Act:
+        """conv1 + bn1 + ReLU + maxpool1 (large_i3d.py:229-232) in the form the input takes, behind the input checks: nothing is launched on an input
+        that is refused."""
+        if records is not None:
+            E.require_cuda(records, "I3Res50")
+            if not (E.STEM_PT and E.STEM_POOL) or "stem_pt" not in P:
+                raise _lib.TedSpadHipError("I3Res50: the stem-record input needs the persistent stem with the fused pool (TEDSPAD_STEM_PT / TEDSPAD_STEM_POOL are off, "
+                                           "or this weight shape has no persistent stem): feed the (B,3,T,H,W) clip instead")
+            st = P["stem_pt"]
+            if records.dim() != 6 or tuple(records.shape[3:]) != (2, records.shape[4], 24) or records.dtype != st.torch_dtype or not records.is_contiguous():
+                raise ValueError("expected contiguous stem records (n, frame pairs, h, 2, w/2, 24) of %s, got %s %s" % (st.torch_dtype, tuple(records.shape), records.dtype))
+            if records.shape[1] < 1 or (records.shape[2] + 1) // 2 < 3 or records.shape[4] < 3:
+                raise ValueError("stem records need at least one frame pair and frames of 5 x 6 pixels for conv1 + maxpool1, got %s" % (tuple(records.shape),))
+            self._check_geometry(int(records.shape[1]), int(records.shape[2]), 2 * int(records.shape[4]), tuple(records.shape))
+            return st.conv_pool(records)                                 # from the records (the LDS-DMA loader of csrc/conv_stem_pt.hip)
+        E.require_cuda(x, "I3Res50")
+        if x.dim() != 5 or x.shape[1] != 3:
+            raise ValueError("expected (B,3,T,H,W), got %s" % (tuple(x.shape),))
+        if x.shape[4] % 2:
+            raise ValueError("W must be even")
+        self._check_geometry(E.conv_out(int(x.shape[2]), 5, 2, 2, 2) // 2, int(x.shape[3]), int(x.shape[4]), tuple(x.shape))
+        st = P["stem_pt"]
+        if E.STEM_PT and taps is None and st.applies(x):
+            # the persistent stem kernel: the 112 x 112 x 8-frame stem tensor is never written
+            if not (E.STEM_POOL and x.shape[3] >= 5 and x.shape[4] >= 6):
+                return E.maxpool(st(x), (1, 3, 3), (1, 2, 2))            # the spatial half of MaxPool3d((2,3,3), 2)
+            if E.STEM_CLIP and (st.VARIANT & 4) and st.direct_applies(x):
+                return st.conv_pool_clip(x)                              # ... straight from the fp32 NCTHW clip: no layout pass either
+            return st.conv_pool(st.layout(x))                            # ... and the spatial half: only the pooled tensor is written
+        a = E.clip_to_act(x, cpad=4, dtype=self.compute_dtype)           # (B,T,H,W/2, 2px x 4ch)
+        a = P["stem"](a, pads=(2, 3, P["stem"].pair_pw), pads_back=(2, 3, 1))   # the same conv in pixel-pair form, K = 5*7*4*8
         if taps is not None:
-            taps[p + "nl"] = a
-        return a
+            taps["stem"] = a
+        return E.maxpool(a, (2, 3, 3), (2, 2, 2))                        # large_i3d.py:138
+
+    def _bottleneck(self, P: dict, p: str, blk: Bottleneck, a: E.Act, h_next, fused: bool, last_l1: bool):
+        """One bottleneck (large_i3d.py:61-84) on the block input `a`, in the first form that applies. h_next: conv1 + bn1 + ReLU of this block where the
+        previous block's fold already made it, else None. fused: the fused forms may be used (no taps). last_l1: layer1's last block, which may pool over
+        frame pairs as well (maxpool2, large_i3d.py:139). Returns (block output, the next block's h_next or None, whether maxpool2 is in the output)."""
+        bf = P.get(p + "frame") if fused else None
+        if bf is not None and bf.applies(a):
+            return bf(a), None, False                                     # conv1 -> conv2 -> conv3 + residual: only the block input and output touch HBM
+        tp = P.get(p + "conv1_tp") if fused else None
+        if h_next is not None:
+            h = h_next                                                    # conv1 + bn1 + ReLU came out of the previous block's tail (BneckTailFold)
+        elif tp is not None and tp.applies(a, (blk.temp_conv, 0, 0)):
+            h = tp(a)                                                     # two frames: both outputs from ONE K = 2*cin GEMM, no products on zero padding
+        else:
+            h = P[p + "conv1"](a, pads=(blk.temp_conv, 0, 0))
+        tail = P.get(p + "tail") if (E.BNECK_TAIL and fused) else None
+        if tail is not None and tail.cmid == 128 and not E.BNECK_TAIL128:
+            tail = None
+        if tail is not None and tail.applies(h, (0, 1, 1)) and (not last_l1 or (E.BNECK_TAIL_POOL and not tail.dual and h.dims[1] % 2 == 0)):
+            # conv2 + bn2 + ReLU + conv3 + bn3 + (residual | downsample branch) + ReLU in one launch: the 64-channel tensor between
+            # the two convolutions is never written (large_i3d.py:69-84)
+            fold = P.get(p + "fold") if not last_l1 else None
+            fold2 = P.get(p + "fold2") if not last_l1 else None
+            if tail.dual and fold2 is not None and fold2.applies(h, (0, 1, 1), a):
+                return (*fold2(h, x2=a), False)                           # the downsample tail and the next block's conv1 + bn1 + ReLU (BneckTailFoldDual)
+            if tail.dual:
+                return tail(h, pads=(0, 1, 1), x2=a), None, False
+            if fold is not None and fold.applies(h, (0, 1, 1), a):
+                return (*fold(h, residual=a), False)                      # ... and the next block's conv1 (3x1x1) + bn1 + ReLU: the block output is not read for it again
+            return tail(h, pads=(0, 1, 1), residual=a, pool_t2=last_l1), None, last_l1
+        h = P[p + "conv2"](h, pads=(0, 1, 1))
+        if blk.downsample is not None and fused and P[p + "conv3"].dual_supported(P[p + "down"], h, a):
+            # layer1.0: conv3 + bn3 and the downsample branch in one launch (the 256-channel downsample tensor
+            # is never written; both branches stay fp32 until the sum)
+            return P[p + "conv3"].call_dual(h, P[p + "down"], a, relu=True), None, False
+        if (p + "dual") in P and fused and P[p + "dual"].dual_p8_supported(h, a, (blk.stride, blk.stride)):
+            # layer2.0 / 3.0 / 4.0: the same pair as ONE GEMM over [W3*s3 | Wd*sd] on the ping-pong kernel
+            return P[p + "dual"].call_dual_p8(h, a, (blk.stride, blk.stride), relu=True), None, False
+        res = P[p + "down"](a, relu=False) if blk.downsample is not None else a
+        if last_l1 and fused and P[p + "conv3"].pool_t2_supported(h):
+            # the block's tail and maxpool2 in one launch: the 256-channel tensor is only written after the temporal
+            # pooling (half the bytes, no separate pool pass)
+            return P[p + "conv3"].call_pool_t2(h, residual=res, relu=True), None, True
+        return P[p + "conv3"](h, residual=res, relu=True), None, False    # bn3 + (+= residual) + ReLU fused
 
     # ---- f16 head-room, observable -----------------------------------------------------------------------------------
     check_saturation = os.environ.get("TEDSPAD_CHECK_SATURATION", "0") == "1"

@@ -152,7 +152,7 @@ def l1_train(y, x, grad_scale, want_y32=False):
     """The train form (tedspad_l1_loss_grad_cl): y = the 16-bit channels-last Act of a 3-channel output (8-channel records, t == 1), x = the fp32
     (n,3,h,w) target. Returns (loss 0-d fp32, dl: the (n,1,h,w,8) gradient Act with sign(float(y) - x) * grad_scale / numel in channels 0-2,
     y32: the fp32 NCHW copy of y or None)."""
-    from .engine import Act
+    from .engine import Act, dtype_code
     n, t, h, w = y.dims
     if t != 1 or tuple(x.shape) != (n, 3, h, w) or x.dtype != torch.float32 or not x.is_cuda:
         raise ValueError("l1_train: y is (%d,%d,%d,%d,8) channels-last, the target must be fp32 cuda (%d,3,%d,%d), got %s %s"
@@ -161,7 +161,7 @@ def l1_train(y, x, grad_scale, want_y32=False):
     dl = Act.empty(n, 1, h, w, 8, y.buf.dtype, y.buf.device)
     loss = torch.empty(1, dtype=torch.float32, device=y.buf.device)
     y32 = torch.empty_like(xc) if want_y32 else None
-    code = _lib.F16 if y.buf.dtype == torch.float16 else _lib.BF16
+    code = dtype_code(y.buf)
     _lib.check(_lib.lib().tedspad_l1_loss_grad_cl(y.ptr, y.ld, xc.data_ptr(), dl.ptr, y32.data_ptr() if want_y32 else None, _l1_ws(xc.device).data_ptr(),
                                                   loss.data_ptr(), n, h * w, C.c_float(grad_scale), code, _stream_ptr()), "tedspad_l1_loss_grad_cl")
     return loss[0], dl, y32

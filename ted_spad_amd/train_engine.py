@@ -151,8 +151,7 @@ def flush_deferred():
         r += 1
 
 
-def _code(t: torch.Tensor) -> int:
-    return _lib.F16 if t.dtype == torch.float16 else _lib.BF16
+_code = E.dtype_code
 
 
 def _ceil_div(a, b):
@@ -313,16 +312,13 @@ class ConvLayer:
             self._dwp_gen = ARENA.gen
             self._db = None
         to, ho, wo = dy.dims[1:]
-        nc = n
-        if n * max(t * h * w * x.ld, to * ho * wo * dy.ld) >= E.MAX_ELEMS or n * to * ho * wo >= E.MAX_WGRAD_PIXELS:
-            nc = min(E.batch_chunk(n, [t * h * w * x.ld, to * ho * wo * dy.ld], E.MAX_ELEMS), E.batch_chunk(n, [to * ho * wo], E.MAX_WGRAD_PIXELS))
         # The weight gradient is off the backward pass's critical path (nothing reads it before the flush): it goes to a side stream, where
         # this L2->LDS-feed-bound kernel runs beside the HBM-bound BatchNorm passes and the data-gradient convs of the layers in front.
         side = side_stream(x.buf.device)
         launches = []
-        for n0 in range(0, n, nc):                      # chunks of whole samples accumulate into the same matrix
-            n1 = min(n, n0 + nc)
-            xs, ds = (Act(x.buf[n0:n1], x.c, x.coff), Act(dy.buf[n0:n1], dy.c, dy.coff)) if nc < n else (x, dy)
+        # chunks of whole samples (32-bit element offsets; the kernel decodes < 2^23 pixels) accumulate into the same matrix
+        for n0, n1 in E.sample_chunks(n, [t * h * w * x.ld, to * ho * wo * dy.ld], E.MAX_ELEMS, [to * ho * wo], E.MAX_WGRAD_PIXELS):
+            xs, ds = x.samples(n0, n1), dy.samples(n0, n1)
             d = pc._desc(n1 - n0, t, h, w, xs.ld, pk, dy.dims[1:], ds.ld, 0, False)
             launches.append((d, xs, ds, pc._ktab(d)))
         if side is not None:

@@ -112,23 +112,23 @@ def stage_dims(geometry):
 
 # ---- the launch sequence ----------------------------------------------------------------------------------------------------------------------------
 
-LAYERS = ((64, 3, 1, (1, 1, 1)), (128, 4, 2, (1, 0, 1, 0)), (256, 6, 2, (1, 0, 1, 0, 1, 0)), (512, 3, 2, (0, 1, 0)))      # i3res50.py:20
-NL_AT = {2: (1, 3), 3: (1, 3, 5)}                                                                                         # i3res50.py:111
+LAYERS = ((64, 3, 1, (1, 1, 1)), (128, 4, 2, (1, 0, 1, 0)), (256, 6, 2, (1, 0, 1, 0, 1, 0)), (512, 3, 2, (0, 1, 0)))      # i3res50.LAYER_PLAN
+NL_AT = {2: (1, 3), 3: (1, 3, 5)}                                                                                         # I3Res50.__init__: nonlocal_mod = 2 on layer2 / layer3
 
 
 def expected_sequence(geometry, use_nl=False, input_form="clip", layers=4):
     """The launch labels of extract_features (of _trunk alone for "taps") on an (n, T, H, W) clip batch, in order. `layers`: a prefix network whose layers
-    behind `layers` are empty. Restates i3res50.py:227-315 and the `applies` / `supported` predicates of engine.py with the default switches."""
+    behind `layers` are empty. Restates I3Res50._stem / _trunk / _bottleneck and the `applies` / `supported` predicates of engine.py with the default switches."""
     assert input_form in INPUT_FORMS
     n, T, H, W = geometry
     generic = input_form == "taps"
     seq = []
-    # the stem (i3res50.py:227-245)
+    # the stem (I3Res50._stem)
     if input_form == "records":
-        seq += ["stem:conv_pool"]                                           # i3res50.py:218
+        seq += ["stem:conv_pool"]                                           # _stem: the records form
     elif input_form in ("wstride", "taps"):
-        seq += ["stem:pair", "maxpool1"]                                    # engine.py:1167 x.stride(4) == 1 fails / i3res50.py:229 taps is None fails
-    elif W % 4 == 0 and input_form != "offset4":                            # engine.py:1213 direct_applies: W % 4 == 0 and a 16-byte aligned base
+        seq += ["stem:pair", "maxpool1"]                                    # StemPT.applies: x.stride(4) == 1 fails / _stem: taps is None fails
+    elif W % 4 == 0 and input_form != "offset4":                            # StemPT.direct_applies: W % 4 == 0 and a 16-byte aligned base
         seq += ["stem:conv_pool_clip"]
     else:
         seq += ["stem:layout", "stem:conv_pool"]
@@ -138,36 +138,36 @@ def expected_sequence(geometry, use_nl=False, input_form="clip", layers=4):
         planes, blocks, stride, tc = LAYERS[li - 1]
         if li == 2:
             if not pooled:
-                seq += ["maxpool2"]                                         # i3res50.py:252
+                seq += ["maxpool2"]                                         # _trunk: maxpool2 unless fused
             t = t // 2
         for i in range(blocks):
             b = "layer%d.%d" % (li, i)
             nl = ["%s:%s" % (b, f) for f in ("nl_theta", "nl_pool", "nl_phi_g", "nl_attention", "nl_out")] if use_nl and i in NL_AT.get(li, ()) else []
             s = stride if i == 0 else 1
-            last_l1 = li == 1 and i == blocks - 1                           # i3res50.py:273 fuse_pool
-            # engine.py:975 BneckFrame.supported: 1024 -> 256 -> 1024 without downsample = layer3.1..5; engine.py:980 applies: (h, w) == (14, 14), a temporal block t == 2
+            last_l1 = li == 1 and i == blocks - 1                           # _trunk: last_l1
+            # BneckFrame.supported: 1024 -> 256 -> 1024 without downsample = layer3.1..5; BneckFrame.applies: (h, w) == (14, 14), a temporal block t == 2
             if not generic and li == 3 and i > 0 and (h, w) == (14, 14) and (not tc[i] or t == 2):
                 seq += [b + ":frame"] + nl
                 continue
             if h_next:
-                h_next = False                                              # i3res50.py:264
-            # i3res50.py:139 conv1_tp behind maxpool2 only; engine.py:752 cout % 128 == 0; engine.py:756 cout >= TPAIR_MIN_COUT = 128 (engine.py:34) and t == 2
+                h_next = False                                              # _bottleneck: h_next taken
+            # I3Res50._pack_block: conv1_tp behind maxpool2 only; TPairConv.supported: cout % 128 == 0; TPairConv.applies: cout >= TPAIR_MIN_COUT = 128 and t == 2
             elif not generic and li >= 2 and tc[i] and planes % 128 == 0 and planes >= 128 and t == 2:
                 seq += [b + ":conv1_tpair"]
             else:
                 seq += [b + ":conv1"]
-            # i3res50.py:154-160 a tail in layer1 / layer2 on stride-1 conv2 (engine.py:799): layer1.0 the two-source form, layer2.0 none
+            # I3Res50._pack_block: a tail in layer1 / layer2 on stride-1 conv2 (BneckTail.supported): layer1.0 the two-source form, layer2.0 none
             has_tail = not generic and li in (1, 2) and s == 1
-            # engine.py:806-808 flat_halo <= 80 KB: (256 + 2 w + 11) * 128 + 33280 (64 channels) or + 32768 (128) <= 81920, i.e. w <= 56 or w <= 58
+            # BneckTail.applies: flat_halo <= 80 KB: (256 + 2 w + 11) * 128 + 33280 (64 channels) or + 32768 (128) <= 81920, i.e. w <= 56 or w <= 58
             fits = w <= (56 if planes == 64 else 58)
             dual = li == 1 and i == 0
-            if has_tail and fits and (not last_l1 or t % 2 == 0):           # i3res50.py:274 `h.dims[1] % 2 == 0` (the last block's tail is never dual)
-                if dual and t == 4:                                         # engine.py:905 BneckTailFoldDual.applies
+            if has_tail and fits and (not last_l1 or t % 2 == 0):           # _bottleneck: `h.dims[1] % 2 == 0` (the last block's tail is never dual)
+                if dual and t == 4:                                         # BneckTailFoldDual.applies
                     seq += [b + ":tail_dual+fold2"]
                     h_next = True
                 elif dual:
                     seq += [b + ":tail_dual"]
-                elif li == 1 and not last_l1 and t == 4:                    # engine.py:861 BneckTailFold.applies (i3res50.py:168-172: layer1's plain blocks but the last)
+                elif li == 1 and not last_l1 and t == 4:                    # BneckTailFold.applies (I3Res50.packed: layer1's plain blocks but the last)
                     seq += [b + ":tail+fold"]
                     h_next = True
                 elif last_l1:
@@ -179,22 +179,22 @@ def expected_sequence(geometry, use_nl=False, input_form="clip", layers=4):
                 continue
             seq += [b + ":conv2"]
             h, w = _out(h, 3, s, 1), _out(w, 3, s, 1)
-            if not generic and i == 0 and li == 1:                          # engine.py:571-572 dual_supported: both 1x1x1 stride 1 with cin == 64
+            if not generic and i == 0 and li == 1:                          # PackedConv.dual_supported: both 1x1x1 stride 1 with cin == 64
                 seq += [b + ":conv3+dual"] + nl
                 continue
-            if not generic and i == 0 and s == 2:                           # i3res50.py:162 + engine.py:606-608 dual_p8_supported: layer2.0 / 3.0 / 4.0 at any size here
+            if not generic and i == 0 and s == 2:                           # I3Res50._pack_block `dual` + PackedConv.dual_p8_supported: layer2.0 / 3.0 / 4.0 at any size here
                 seq += [b + ":dual_p8"] + nl
                 continue
             if i == 0:
-                seq += [b + ":down"]                                        # i3res50.py:306
-            if not generic and last_l1 and t >= 2:                          # engine.py:550 pool_t2_supported: cin 64 and t >= 2, odd t included
+                seq += [b + ":down"]                                        # _bottleneck: the downsample branch on its own
+            if not generic and last_l1 and t >= 2:                          # PackedConv.pool_t2_supported: cin 64 and t >= 2, odd t included
                 seq += [b + ":conv3+pool_t2"]
                 pooled = True
             else:
                 seq += [b + ":conv3"]
             seq += nl
     if layers < 2 and not pooled:
-        seq += ["maxpool2"]                                                 # an empty layer2 is still entered (i3res50.py:251-253)
+        seq += ["maxpool2"]                                                 # an empty layer2 is still entered (_trunk's layer loop)
     if not generic:
         seq += ["avgpool"]
     return seq

@@ -457,3 +457,28 @@ def test_device_flag_reads_its_tensor_once_and_on_demand():
         assert f._t is None                       # the tensor is dropped after the first read
     d = {"skipped": DeviceFlag(torch.tensor(0.0))}
     assert not d["skipped"] and (True if not d["skipped"] else False)
+
+
+def test_sample_chunks_and_act_sample_range(monkeypatch):
+    """engine.sample_chunks: ranges of whole samples under the limit the caller reads from the module when it calls, the whole batch as (0, n) alone, a
+    loud failure for a single sample that does not fit; Act.samples: the same channel view of samples [n0, n1), the Act itself for the whole batch."""
+    per = 100
+    assert list(E.sample_chunks(6, [per], 3 * per + 1)) == [(0, 3), (3, 6)]
+    assert list(E.sample_chunks(5, [per, 7], 2 * per + 1)) == [(0, 2), (2, 4), (4, 5)]
+    for n in (1, 4):
+        assert list(E.sample_chunks(n, [per], E.MAX_ELEMS)) == [(0, n)]
+    assert list(E.sample_chunks(6, [per], 1 << 20, [10], 2 * 10 + 1)) == [(0, 2), (2, 4), (4, 6)]     # a second (sizes, limit) pair: the weight gradient's pixel count
+    with pytest.raises(_lib.TedSpadHipError, match="single sample"):
+        list(E.sample_chunks(2, [1 << 31], E.MAX_ELEMS))
+    monkeypatch.setattr(E, "MAX_ELEMS", 3 * per + 1)              # lowered after import, as the GPU tests do: read at call time
+    assert list(E.sample_chunks(6, [per], E.MAX_ELEMS)) == [(0, 3), (3, 6)]
+    with pytest.raises(_lib.TedSpadHipError, match="single sample"):
+        list(E.sample_chunks(2, [3 * per + 1], E.MAX_ELEMS))
+    a = E.Act(torch.zeros((5, 2, 3, 4, 32), dtype=torch.float16), 8, 16)
+    assert a.samples(0, 5) is a
+    for n0, n1 in ((0, 2), (2, 4), (4, 5)):
+        s = a.samples(n0, n1)
+        assert (s.c, s.coff, s.ld, s.cpad) == (a.c, a.coff, a.ld, a.cpad) and s.dims == (n1 - n0, 2, 3, 4)
+        assert s.ptr == a.ptr + n0 * 2 * 3 * 4 * 32 * 2
+    assert E.Act(a.buf, 8, 0, 4).samples(1, 3).cpad == 4
+    assert E.dtype_code(a.buf) == _lib.F16 and E.dtype_code(a.buf.bfloat16()) == _lib.BF16

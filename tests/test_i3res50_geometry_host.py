@@ -24,7 +24,7 @@ def test_entry_reaches_what_the_table_says(name):
 
 
 def test_sequence_of_a_production_clip_spelled_out():
-    """16 x 216^2 takes 16 x 224^2's forms (i3res50.py:227-315 read at t = 4 -> 2 and 53 / 27 / 14 / 7 pixel frames), written out by hand."""
+    """16 x 216^2 takes 16 x 224^2's forms (I3Res50._stem / _bottleneck read at t = 4 -> 2 and 53 / 27 / 14 / 7 pixel frames), written out by hand."""
     blocks = lambda li, forms: ["layer%d.%d:%s" % (li, i, f) for i, fs in enumerate(forms) for f in fs]
     want = (["stem:conv_pool_clip"] +
             blocks(1, [["conv1", "tail_dual+fold2"], ["tail+fold"], ["tail+pool_t2"]]) +
